@@ -2,7 +2,7 @@
 """Headline benchmark: CSR SpMM + SDDMM-backward, N=1e6 rows, 27 nnz/row, 32 RHS, fp32/int32
 (BASELINE.json configs[1], "C2"), on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N>1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run)
 
 A step = one pass of the hot path over one batch of synthetic input: `sparse_mm(A, B)` forward
 followed by its backward for a dense upstream gradient (K1 SpMM, K3 SDDMM → gradA at A's pattern,
@@ -14,9 +14,15 @@ RCCL all-gather of the forward result is timed separately and reported in `allga
 value = algorithmic GB/s of the whole job = N · 1188 MB / max-over-ranks step time
 (476 MB forward + 712 MB minimum fused backward).  One JSON line on rank 0.
 
-The line also carries `c5`: BASELINE.json configs[4] (batched CSR, 64 items of N=131072, 27 nnz/row, 16 RHS, bf16)
-sharded over the N ranks through `torchsparsegradutils_amd.parallel` — compute-only and end-to-end (with the RCCL
-all-gather of the result) reported separately.  `--no-c5` skips it.
+A plain run sets up, warms up, times ONE loop of exactly K steps (`ms_per_step` = that loop's time / K) and prints
+the line.  `--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (a fixed,
+seeded sample: see dump_outputs).  Everything else is measured with `--full` only: more timed loops of K steps,
+the step's halves and kernels (roofline), HIP-graph replay, the host's share, the all-gather, and the legs below.
+
+With `--full` the line also carries `c5`: BASELINE.json configs[4] (batched CSR, 64 items of N=131072, 27 nnz/row,
+16 RHS, bf16) sharded over the N ranks through `torchsparsegradutils_amd.parallel` — compute-only and end-to-end
+(with the RCCL all-gather of the result) reported separately.  `--no-c5` skips it (likewise `--no-patterns`,
+`--no-published`, `--no-cpu-baseline` for the other legs of a full run).
 """
 
 import argparse
@@ -37,7 +43,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is 
 
 
 CLOCK_WARM_MS = 120.0
-TIMED_LOOPS = 5          # timed loops of exactly --steps steps; the headline is their median
+TIMED_LOOPS = 5          # --full: timed loops of exactly --steps steps (the headline's loop and TIMED_LOOPS - 1 more)
+DUMP_SEED = 0            # --dump-outputs: the sample of rows / stored entries written (fixed: two builds compare file for file)
+DUMP_ELEMS = 1 << 21     # dense outputs: rows sampled so that rows x columns stays within this (8 MB of fp32 each)
+DUMP_ENTRIES = 1 << 19   # sparse gradient: stored entries sampled
 
 
 def alg_bytes(n, nnz, p, I=4, V=4, items=1):
@@ -617,6 +626,32 @@ def published_shapes_leg(dev, steps, with_cpu):
     return out
 
 
+def dump_outputs(out_dir, C, gA, gB):
+    """`--dump-outputs`: what one step hands its caller — C = A·B, gradA (CSR at A's pattern: values, row pointer, column indices)
+    and gradB — as <out_dir>/<name>.npy.  The whole of it is 364 MB at C2, so a fixed, seeded sample is written: the same rows of C,
+    gradB and the row pointer (at most DUMP_ELEMS elements of C), DUMP_ENTRIES stored entries of gradA (values, column indices).
+    Floating-point results keep fp32 / fp64 (bf16 as fp32), indices are written as float64 (exact)."""
+    import numpy as np
+
+    n, p = C.shape
+    nnz = gA.values().numel()
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = torch.from_numpy(np.sort(rng.choice(n, size=min(n, max(1, DUMP_ELEMS // p)), replace=False))).to(C.device)
+    ents = torch.from_numpy(np.sort(rng.choice(nnz, size=min(nnz, DUMP_ENTRIES), replace=False))).to(C.device)
+    with torch.no_grad():
+        arrays = {
+            "C": C.detach()[rows],
+            "gradB": gB.detach()[rows],
+            "gradA_values": gA.detach().values()[ents],
+            "gradA_crow_indices": gA.detach().crow_indices()[rows],
+            "gradA_col_indices": gA.detach().col_indices()[ents],
+        }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = (t if t.dtype == torch.float64 else t.float()) if t.is_floating_point() else t.double()
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -628,7 +663,14 @@ def main():
     ap.add_argument("--no-c5", action="store_true")
     ap.add_argument("--no-patterns", action="store_true")
     ap.add_argument("--no-published", action="store_true", help="skip the shapes of the reference's published tables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (C, gradA, gradB: a fixed sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: more timed loops, kernels and roofline, graph replay, host "
+                         "share, all-gather, C5, other patterns, published shapes, CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N`: this process has made no GPU call yet — it starts the N ranks as fresh child processes
@@ -676,6 +718,12 @@ def main():
         gA, gB = torch.autograd.grad(C, (A, B), G)
         return C
 
+    def step_outputs():
+        # the same step, handing back everything the caller receives (the last step of the timed loop: what --dump-outputs writes)
+        C = sparse_mm(A, B)
+        gA, gB = torch.autograd.grad(C, (A, B), G)
+        return C, gA, gB
+
     def step_backward_call():
         # the reference harness' form (benchmarks/benchmark_utils.py:194-198): `.backward()` accumulates into .grad —
         # torch's AccumulateGrad deep-copies the sparse CSR gradient (crow, col, values) on the first accumulation
@@ -720,11 +768,16 @@ def main():
             torch.cuda.synchronize(dev)
     torch.cuda.synchronize(dev)
 
-    def timed_loop(fn):
+    kept = {}
+
+    def timed_loop(fn, last=None):
+        # exactly --steps calls; with `last`, the final call is last() and its results are kept
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - (last is not None)):
             fn()
+        if last is not None:
+            kept["outputs"] = last()
         barrier()
         el = time.perf_counter() - t0
         if world > 1:
@@ -733,11 +786,77 @@ def main():
             el = float(tt.item())
         return el / args.steps * 1e3
 
-    # The timed region: TIMED_LOOPS loops of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and reduced
-    # with MAX over the ranks; `ms_per_step` is the MEDIAN loop (a single 20-step loop is ~5 ms at C2: one sample of that length moved
-    # the headline by +-3 % between boxes).  Every loop's figure is in `ms_per_step_loops`.
-    loops_ms = [timed_loop(step) for _ in range(TIMED_LOOPS)]
-    ms_per_step = sorted(loops_ms)[len(loops_ms) // 2]
+    # The timed region: ONE loop of EXACTLY --steps steps, bracketed by barrier + synchronize on both sides and reduced with MAX over
+    # the ranks; `ms_per_step` is its time per step.  Its last step hands its results back (--dump-outputs).  With --full,
+    # TIMED_LOOPS - 1 more loops of the same length follow (a single 20-step loop is ~5 ms at C2: one sample of that length moved the
+    # figure by +-3 % between boxes): every loop's figure is in `ms_per_step_loops`, their median in `ms_per_step_median_of_loops`.
+    ms_per_step = timed_loop(step, last=step_outputs)
+    loops_ms = [ms_per_step] + [timed_loop(step) for _ in range(TIMED_LOOPS - 1 if args.full else 0)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *kept["outputs"])
+    kept.clear()
+    plan = _pattern.from_csr(A.detach())
+    plan_stats = {"cache_entries": _pattern.cache_stats()[0], "plan_bytes_resident": _pattern.cache_stats()[1]}   # what the steps built
+    Bd, vd = B.detach(), val
+    lat_f = _ops._lattice_cfg(plan, be.LAT_SPMM, Bd)
+    lat_s = _ops._lattice_cfg(plan, be.LAT_SDDMM, Bd, G)
+    lat_t = _ops._lattice_cfg(plan, be.LAT_SPMMT, G)
+    lattice = lat_f is not None and lat_s is not None and lat_t is not None
+
+    def headline_line():
+        """The fields of the line that a plain run measures (the headline and its configuration)."""
+        total_bytes = ab["fwd_bwd"] * world
+        value = total_bytes / (ms_per_step * 1e-3) / 1e9
+        flops = 3 * 2 * nnz * p * world
+        return {
+            "metric": "CSR SpMM+SDDMM achieved HBM GB/s (algorithmic bytes), N=1e6 nnz/row=27 RHS=32, fwd+bwd",
+            "value": round(value, 2),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 5),
+            "ms_per_step_note": f"one timed loop of exactly {args.steps} steps (barrier + synchronize on both sides, max over ranks), "
+                                "its time per step",
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": f"C2: CSR SpMM+backward, periodic 27-pt stencil {nx}x{ny}x{nz} (N={n}, nnz={nnz}), {p} RHS, "
+                            "fp32 values / int32 indices, sparse_mm fwd + backward through the autograd API; one such item per GPU",
+                "algorithmic_bytes_per_step_per_gpu": ab["fwd_bwd"],
+                "timed_step": "sparse_mm + torch.autograd.grad (ms_per_step); the same step with C.backward(G) into .grad "
+                              "(reference harness form, includes torch's AccumulateGrad copies of the sparse gradient) is "
+                              "ms_per_step_backward_call (--full)",
+                "first_steps_ms": [round(x, 2) for x in first_ms],
+                "warmup_steps_run": warm_steps,
+                "plan_policy": f"first sight of a pattern: plan-free gather kernels + transposed pattern; from use {_ops.PLAN_AFTER_USES + 1} on "
+                               + ("(lattice stencil: the lattice plan — row classes, found by two row-analysis kernels — is built at FIRST sight, "
+                                  "first_steps_ms[0] includes that; every step runs on the plane-march / plane-sweep kernels and neither a "
+                                  "transposed pattern nor, for a periodic stencil, a transposed plan is ever built)" if lattice else
+                                  ("the row-pair plans are built on a worker thread + side stream while the steps keep running plan-free "
+                                   "(first_steps_ms[1:] are such steps); the warm-up joins the build" if _ops.PLAN_ASYNC else
+                                   "the row-pair plans are built inline (first_steps_ms[1] includes the build)")),
+                "first_step_note": "torch.autograd imports torch.fx.experimental.symbolic_shapes (sympy) inside the first backward that is given "
+                                   "explicit output gradients (150-450 ms); the package performs that import when it is itself "
+                                   "imported (TSGU_PREFETCH_IMPORTS=0 restores torch's lazy behaviour), so first_steps_ms[0] does not contain it",
+                "plan_join_ms_after_3_steps": round(plan_join_ms, 1),
+                "plans": plan_stats,
+            },
+            "gflops": round(flops / (ms_per_step * 1e-3) / 1e9, 1),
+            "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBS, 4),
+        }
+
+    ab = alg_bytes(n, nnz, p)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line()), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     step_backward_call()
     ms_backward_call = timed_loop(step_backward_call)
     A.grad = None
@@ -860,17 +979,9 @@ def main():
     ms_device = time_events(step, n_ev, dev, hold_ms=hold_ms, settle=30)
 
     # ---- per-kernel durations (HIP events on the launch stream), same resident operands ----
-    plan = _pattern.from_csr(A.detach())
-    plan_stats = {"cache_entries": _pattern.cache_stats()[0], "plan_bytes_resident": _pattern.cache_stats()[1]}   # what the steps built
     pt = plan.transposed      # (only the plan-free reference kernels below need the transposed pattern on a lattice)
-    Bd, vd = B.detach(), val
     reps = max(args.steps, 20)
-    ab = alg_bytes(n, nnz, p)
     kern_alt = {}
-    lat_f = _ops._lattice_cfg(plan, be.LAT_SPMM, Bd)
-    lat_s = _ops._lattice_cfg(plan, be.LAT_SDDMM, Bd, G)
-    lat_t = _ops._lattice_cfg(plan, be.LAT_SPMMT, G)
-    lattice = lat_f is not None and lat_s is not None and lat_t is not None
     lat_f_is_march = lat_f[1] if lat_f is not None else None
     rp_t = rp_f = rp_s = None
     kern_alone = None
@@ -957,19 +1068,11 @@ def main():
 
     def make_line(allgather, c5, patterns, cpu, published=None, fresh=None):
         """The ONE JSON line of this run (rank 0) from what has been measured so far."""
-        total_bytes = ab["fwd_bwd"] * world
-        value = total_bytes / (ms_per_step * 1e-3) / 1e9
-        flops = 3 * 2 * nnz * p * world
-        line = {
-            "metric": "CSR SpMM+SDDMM achieved HBM GB/s (algorithmic bytes), N=1e6 nnz/row=27 RHS=32, fwd+bwd",
-            "value": round(value, 2),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 5),
+        line = headline_line()
+        line["ms_per_step_note"] += f"; ms_per_step_loops: it and {TIMED_LOOPS - 1} more loops of the same length"
+        line.update({
             "ms_per_step_loops": [round(x, 5) for x in loops_ms],
-            "ms_per_step_note": f"median of {TIMED_LOOPS} timed loops of exactly {args.steps} steps each (barrier + synchronize on both sides of every loop, max over ranks)",
+            "ms_per_step_median_of_loops": round(sorted(loops_ms)[len(loops_ms) // 2], 5),
             "ms_per_step_backward_call": round(ms_backward_call, 5),
             "ms_per_step_single_thread_autograd": None if ms_single_thread is None else round(ms_single_thread, 5),
             "host_ms_per_step": None if host_ms is None else round(host_ms, 5),
@@ -982,34 +1085,6 @@ def main():
             "ms_per_step_graph_replay": None if ms_graph is None else round(ms_graph, 5),
             "ms_per_step_graph_replay_4": None if ms_graph4 is None else round(ms_graph4, 5),
             "graph_replay_note": graph_note,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"C2: CSR SpMM+backward, periodic 27-pt stencil {nx}x{ny}x{nz} (N={n}, nnz={nnz}), {p} RHS, "
-                            "fp32 values / int32 indices, sparse_mm fwd + backward through the autograd API; one such item per GPU",
-                "algorithmic_bytes_per_step_per_gpu": ab["fwd_bwd"],
-                "timed_step": "sparse_mm + torch.autograd.grad (ms_per_step); the same step with C.backward(G) into .grad "
-                              "(reference harness form, includes torch's AccumulateGrad copies of the sparse gradient) is ms_per_step_backward_call",
-                "first_steps_ms": [round(x, 2) for x in first_ms],
-                "warmup_steps_run": warm_steps,
-                "plan_policy": f"first sight of a pattern: plan-free gather kernels + transposed pattern; from use {_ops.PLAN_AFTER_USES + 1} on "
-                               + ("(lattice stencil: the lattice plan — row classes, found by two row-analysis kernels — is built at FIRST sight, "
-                                  "first_steps_ms[0] includes that; every step runs on the plane-march / plane-sweep kernels and neither a "
-                                  "transposed pattern nor, for a periodic stencil, a transposed plan is ever built)" if lattice else
-                                  ("the row-pair plans are built on a worker thread + side stream while the steps keep running plan-free "
-                                   "(first_steps_ms[1:] are such steps); the warm-up joins the build" if _ops.PLAN_ASYNC else
-                                   "the row-pair plans are built inline (first_steps_ms[1] includes the build)")),
-                "first_step_note": "torch.autograd imports torch.fx.experimental.symbolic_shapes (sympy) inside the first backward that is given "
-                                   "explicit output gradients (150-450 ms); the package performs that import when it is itself "
-                                   "imported (TSGU_PREFETCH_IMPORTS=0 restores torch's lazy behaviour), so first_steps_ms[0] does not contain it",
-                "plan_join_ms_after_3_steps": round(plan_join_ms, 1),
-                "plans": plan_stats,
-            },
-            "gflops": round(flops / (ms_per_step * 1e-3) / 1e9, 1),
-            "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBS, 4),
             "roofline": {
                 "bound": "hbm",
                 "kernel": dominant,
@@ -1043,7 +1118,7 @@ def main():
             "patterns": patterns,
             "published_shapes": published,
             "fresh_index_tensors": fresh,
-        }
+        })
         if allgather is not None:
             line["allgather"] = allgather
         return line

@@ -1,7 +1,8 @@
 """bench.py's N > 1 code path on a one-GPU box: two ranks share cuda:0 and talk over gloo (RCCL refuses two ranks on one
 device; `TSGU_BENCH_TEST_BACKEND` is a test hook).  Checks that both ranks get through the barriers, the max-over-ranks timing,
-the sharded C5 leg (plain and chunk-overlapped gathers) and the all-gather leg, and that rank 0 prints ONE well-formed line —
-the numbers of such a run mean nothing.  (Collected last: the file name sorts after the parity tests.)  Needs an MI355X: `pytest -m gpu`."""
+the sharded C5 leg (plain and chunk-overlapped gathers) and the all-gather leg (all three: `--full`), and that rank 0 prints
+ONE well-formed line — the numbers of such a run mean nothing.  (Collected last: the file name sorts after the parity tests.)
+Needs an MI355X: `pytest -m gpu`."""
 
 import json
 import os
@@ -24,7 +25,7 @@ def test_bench_runs_with_two_ranks(form):
     env = dict(os.environ, TSGU_BENCH_TEST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"]
     if form == "launcher":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", "29519"] + tail
@@ -62,7 +63,7 @@ def test_bench_prints_its_line_when_a_secondary_leg_stalls():
                TSGU_BENCH_LEGS_TIMEOUT="5")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"]
     try:
         out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     except subprocess.TimeoutExpired:
