@@ -642,6 +642,37 @@ int tsgu_coldot(int vtype, int64_t n, int64_t p, const void* X, int64_t ldx,
                 const void* Y, int64_t ldy, void* partial, void* out,
                 int device, void* stream);
 
+/*
+ * Segmented log-sum-exp (sparse_logsumexp / sparse_bidir_logsumexp).
+ * replaces: the scatter amax / exp / scatter sum / log of  torchsparsegradutils/sparse_logsumexp.py:10-73 (_scatter_logsumexp),
+ *           its callers per axis                             sparse_logsumexp.py:105-138 (_logsumexp_2d),
+ *           per batch item                                   sparse_logsumexp.py:141-172 (_logsumexp_batched),
+ *           both axes into one padded buffer                 sparse_logsumexp.py:175-243 (_bidir_2d / _bidir_batched)
+ *
+ * out[group g] = log( sum_{k in [ptr[g], ptr[g+1])} exp(val[perm ? perm[k] : k])  +  zeros_g ),
+ * zeros_g = axis_len - (ptr[g+1] - ptr[g]) when include_zeros (every stored entry counts, duplicates too), else 0.
+ * NaN in a group -> NaN; +inf -> +inf; no values and no zeros -> -inf.  bf16 values accumulate in fp32 (one rounding at the end).
+ * The row direction of a CSR pattern is (crow, no perm); the column direction its cached transpose (tptr, perm into A's values);
+ * a whole matrix / batch item is one group (ptr = item boundaries, axis_len = rows * cols).
+ * Output: group g is written at out[(g / groups_per_item) * item_stride + g % groups_per_item]; positions
+ * [groups_per_item, item_stride) of every item are set to -inf (the padded buffer of the bidirectional call, no separate fill).
+ * Balanced by entries, not by groups; deterministic (no float atomics: partials of groups that span several entry ranges are
+ * merged in a fixed order).  `workspace` (16-byte aligned) holds tsgu_segment_logsumexp_workspace(vtype, nnz) bytes.
+ */
+int tsgu_segment_logsumexp_workspace(int vtype, int64_t nnz, int64_t* bytes_host);
+int tsgu_segment_logsumexp(int vtype, int itype, int64_t n_groups, int64_t nnz, const void* ptr, const void* perm,
+                           const void* val, int include_zeros, int64_t axis_len, void* out, int64_t groups_per_item,
+                           int64_t item_stride, void* workspace, int64_t workspace_bytes, int device, void* stream);
+/*
+ * Gradient of the stored values, in their stored order (the backward of sparse_logsumexp.py:10-73 through autograd):
+ *   grad[k] = g_grp[grp(k)] * exp(val[k] - lse_grp[grp(k)])  +  g_idx[idx[k]] * exp(val[k] - lse_idx[idx[k]])
+ * grp(k): the group of [ptr[g], ptr[g+1]) holding k (found from ptr inside the kernel; n_groups = len(ptr) - 1);
+ * either direction may be absent (ptr = NULL / idx = NULL).  One streaming pass, no atomics.
+ */
+int tsgu_segment_logsumexp_backward(int vtype, int itype, int64_t nnz, const void* val, const void* ptr, int64_t n_groups,
+                                    const void* g_grp, const void* lse_grp, const void* idx, const void* g_idx,
+                                    const void* lse_idx, void* grad, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,13 +1,14 @@
 """MI355X-native (gfx950) implementation of torchsparsegradutils' sparse hot path.
 
-Drop-in names for ``sparse_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve``
-(reference ``torchsparsegradutils/__init__.py:1-16``); the arithmetic runs in hand-written HIP
+Drop-in names for ``sparse_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` / ``sparse_logsumexp`` /
+``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``); the arithmetic runs in hand-written HIP
 kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
 from ._backend import poll_errors
 from ._compat import linalg_solve_triangular_compat
 from ._pattern import wait_for_plans
+from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
 from .sparse_solve import (
@@ -22,12 +23,15 @@ __all__ = [
     "sparse_triangular_solve",
     "sparse_generic_solve",
     "sparse_generic_lstsq",
+    "sparse_logsumexp",
+    "sparse_bidir_logsumexp",
     "SparseGenericLstsq",
     "wait_for_plans",
     "poll_errors",
     "SparseMatMul",
     "SparseTriangularSolve",
     "SparseGenericSolve",
+    "SparseLogSumExp",
     "linalg_solve_triangular_compat",
 ]
 

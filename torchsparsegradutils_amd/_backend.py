@@ -59,6 +59,13 @@ SIGNATURES = {
          _int, _ptr],
     ),
     "tsgu_coo_sddmm": (_int, [_int, _int, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _dbl, _i64, _int, _ptr]),
+    "tsgu_segment_logsumexp_workspace": (_int, [_int, _i64, ctypes.POINTER(_i64)]),
+    "tsgu_segment_logsumexp": (
+        _int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _int, _i64, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr],
+    ),
+    "tsgu_segment_logsumexp_backward": (
+        _int, [_int, _int, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr],
+    ),
     "tsgu_csr_mm_backward": (
         _int,
         [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _i64,
@@ -765,6 +772,59 @@ def coo_sddmm(row, col, G, B, alpha: float = 1.0):
             "tsgu_coo_sddmm",
         )
     return out
+
+
+def segment_logsumexp_workspace_bytes(dtype: torch.dtype, nnz: int) -> int:
+    """Workspace bytes tsgu_segment_logsumexp needs for `nnz` entries of value type `dtype`."""
+    out = ctypes.c_int64(0)
+    check(load_library().tsgu_segment_logsumexp_workspace(_VTYPE[dtype], nnz, ctypes.byref(out)),
+          "tsgu_segment_logsumexp_workspace")
+    return int(out.value)
+
+
+def segment_logsumexp(ptr, perm, val, out, n_groups: int, nnz: int, include_zeros: bool, axis_len: int,
+                      groups_per_item: int, item_stride: int, workspace):
+    """out[group] = log Σ exp over the segments [ptr[g], ptr[g+1]) of val (through perm when given), plus the absent entries of
+    each group when include_zeros; group g lands at out[(g // groups_per_item) * item_stride + g % groups_per_item] and the
+    padding of every item is set to -inf.  `out` may be a view into a larger buffer (only its data pointer is used)."""
+    lib = load_library()
+    dev = require_device(ptr, perm, val, out, workspace)
+    if perm is not None and perm.dtype != ptr.dtype:
+        raise RuntimeError(f"index dtypes differ: {ptr.dtype} and {perm.dtype}")
+    if out.dtype != val.dtype:
+        raise RuntimeError(f"output dtype {out.dtype} differs from the values' {val.dtype}")
+    with torch.cuda.device(dev):
+        check(
+            lib.tsgu_segment_logsumexp(
+                vtype_of(val), itype_of(ptr), n_groups, nnz, _p(ptr), _p(perm), _p(val), int(bool(include_zeros)), axis_len,
+                _p(out), groups_per_item, item_stride, _p(workspace), workspace.numel() * workspace.element_size(),
+                dev.index, _stream(dev),
+            ),
+            "tsgu_segment_logsumexp",
+        )
+
+
+def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx, n_groups: int):
+    """grad[k] = g_grp[grp(k)]·exp(val[k] − lse_grp[grp(k)]) + g_idx[idx[k]]·exp(val[k] − lse_idx[idx[k]]) in stored order
+    (either direction may be None)."""
+    lib = load_library()
+    dev = require_device(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx)
+    itp = ptr if ptr is not None else idx
+    if ptr is not None and idx is not None and ptr.dtype != idx.dtype:
+        raise RuntimeError(f"index dtypes differ: {ptr.dtype} and {idx.dtype}")
+    for t in (g_grp, lse_grp, g_idx, lse_idx):
+        if t is not None and (t.dtype != val.dtype or not t.is_contiguous()):
+            raise RuntimeError("group vectors must be contiguous and of the values' dtype")
+    grad = torch.empty_like(val)
+    with torch.cuda.device(dev):
+        check(
+            lib.tsgu_segment_logsumexp_backward(
+                vtype_of(val), itype_of(itp), val.numel(), _p(val), _p(ptr), n_groups, _p(g_grp), _p(lse_grp), _p(idx),
+                _p(g_idx), _p(lse_idx), _p(grad), dev.index, _stream(dev),
+            ),
+            "tsgu_segment_logsumexp_backward",
+        )
+    return grad
 
 
 def csr_sptrsm(ptr, idx, val, B, n: int, lower: bool, unit: bool, perm=None, wg_per_cu: int = 1):

@@ -15,6 +15,8 @@ gathers · mul · sum  :186-205              :func:`sddmm`, in entry chunks: the
 ``torch.sparse.mm(A.t(), G)``  :229        :func:`spmm` on the cached transposed pattern
 ``torch.triangular_solve``  _compat:42-48  :func:`sptrsm` (the same call, same flags)
 column dots of the Krylov loops            :func:`coldot`
+``_scatter_logsumexp``  sparse_logsumexp.py:10-73   :func:`segment_logsumexp` / :func:`segment_logsumexp_backward` on the
+                                           segments of a cached pattern (every stored entry is one term)
 =========================================  ====================================================================
 """
 
@@ -103,3 +105,39 @@ def coldot(X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
     """Column-wise dot products of two (n, p) arrays -> (p,)."""
     _cpu_only(X, Y)
     return (X * Y).sum(dim=0)
+
+
+def segment_logsumexp(ptr: torch.Tensor, perm, val: torch.Tensor, n_groups: int, include_zeros: bool, axis_len: int) -> torch.Tensor:
+    """log Σ exp over the segments [ptr[g], ptr[g+1]) of val (through perm when given), plus one exp(0) per absent entry of the
+    axis when include_zeros.  Shifted by the group's maximum (0 at least when absent entries count; 0 when it is not finite),
+    so that NaN stays NaN, +inf gives +inf and an empty group gives -inf.  bf16 values accumulate in fp32."""
+    _cpu_only(ptr, perm, val)
+    acc = torch.float32 if val.dtype == torch.bfloat16 else val.dtype
+    v = val.reshape(-1) if perm is None else val.reshape(-1).index_select(0, perm.to(torch.int64))
+    v = v.to(acc)
+    counts = (ptr[1:] - ptr[:-1]).to(torch.int64)
+    grp = torch.repeat_interleave(torch.arange(n_groups), counts, output_size=v.numel())
+    top = torch.full((n_groups,), float("-inf"), dtype=acc).scatter_reduce(0, grp, v, "amax", include_self=True)
+    top = torch.where(torch.zeros(n_groups, dtype=acc).index_add(0, grp, v.isnan().to(acc)) > 0, float("nan"), top)
+    zeros = (axis_len - counts).to(acc) if include_zeros else torch.zeros(n_groups, dtype=acc)
+    shift = torch.where(zeros > 0, top.clamp(min=0.0), top)
+    shift = torch.where(shift.isfinite(), shift, torch.zeros_like(shift))
+    total = torch.zeros(n_groups, dtype=acc).index_add(0, grp, (v - shift[grp]).exp())
+    total = total + torch.where(zeros > 0, zeros * (-shift).exp(), torch.zeros_like(total))
+    out = torch.where(total == 0, float("-inf"), shift + total.log())
+    return out.to(val.dtype)
+
+
+def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx) -> torch.Tensor:
+    """grad[k] = g_grp[grp(k)]·exp(val[k] − lse_grp[grp(k)]) + g_idx[idx[k]]·exp(val[k] − lse_idx[idx[k]]) in stored order."""
+    _cpu_only(val, ptr, idx)
+    acc = torch.float32 if val.dtype == torch.bfloat16 else val.dtype
+    v = val.reshape(-1).to(acc)
+    grad = torch.zeros_like(v)
+    if ptr is not None:
+        grp = torch.repeat_interleave(torch.arange(ptr.numel() - 1), (ptr[1:] - ptr[:-1]).to(torch.int64), output_size=v.numel())
+        grad = grad + g_grp.to(acc)[grp] * (v - lse_grp.to(acc)[grp]).exp()
+    if idx is not None:
+        j = idx.reshape(-1).to(torch.int64)
+        grad = grad + g_idx.to(acc)[j] * (v - lse_idx.to(acc)[j]).exp()
+    return grad.to(val.dtype)

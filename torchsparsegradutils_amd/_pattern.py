@@ -1008,6 +1008,14 @@ def from_csr(A: torch.Tensor) -> RowGather:
     return RowGather(crow, col, A.size(-2), A.size(-1), core=_core_for("csr", (crow, col), A.shape))
 
 
+def from_csc(A: torch.Tensor) -> RowGather:
+    """Plan for a CSC tensor, 2-D or batched 3-D: its columns as the groups of a row gather (ccol, row_indices) of Aᵀ, so that
+    ``.transposed`` walks A's rows (with a ``perm`` into A's value array)."""
+    ccol, row = A.ccol_indices(), A.row_indices()
+    shape_t = tuple(A.shape[:-2]) + (A.size(-1), A.size(-2))
+    return RowGather(ccol, row, A.size(-1), A.size(-2), core=_core_for("csc", (ccol, row), shape_t))
+
+
 def from_coo_2d(indices: torch.Tensor, shape, coalesced: bool) -> RowGather:
     """Plan for 2-D COO indices (2, nnz).  Coalesced input is already row-sorted; otherwise the
     entries are visited in a stable row order through ``perm`` (duplicates stay separate)."""
