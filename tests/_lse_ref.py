@@ -35,6 +35,33 @@ def group_lse(ptr, vals, axis_len=None):
     return out, counts + (zeros if axis_len is not None else 0)
 
 
+def fwd_bound(lse_ref, k, n_pieces, eps, lane_max=48, wave=64):
+    """Bound on |kernel result − float64 value| of one group's log-sum-exp, for a kernel accumulating with machine epsilon
+    `eps`: the smaller of a term-count form and a reduction-depth form, both plus 4ε·|lse| for the shift and the final add.
+
+    Term-count form, (2k + 8)·ε: k rounded exp terms summed after the shift by the group's maximum (the total is ≥ 1), each
+    addition and each exp costing at most ε relative, and a few ε for the log and the absent-entry term.
+
+    Depth form, (L + 6 + 3·(⌈P/64⌉ + 6) + 2 + ln(1 + k) + 8)·ε, with P the group's range pieces (`n_pieces`) and
+    L = kLseLaneMax.  The sums are of positive terms, so the relative error of a total is bounded by the longest chain of
+    roundings from a term to it, not by the number of terms:
+      - a piece: one lane adds ≤ L terms in sequence (the lane path takes ≤ L entries, the wave path ≤ R/64 ≤ L per lane), then
+        a 6-level butterfly: L + 6;
+      - the merge: each lane combines ⌈P/64⌉ partials in sequence, then a 6-level butterfly; a combine rounds an exp, a product
+        and a sum: 3·(⌈P/64⌉ + 6);
+      - each exp term costs ≤ 2ε, and its argument v − m is rounded by ≤ ε/2·|v − m|: weighted by the terms, Σ pᵢ·|ln tᵢ| is an
+        entropy ≤ ln k, so ≤ ln(1 + k)·ε over the shift and the rescaling of partials together;
+      - the absent entries (one product and one exp), the log and its addition: 8.
+    An error δ relative in the total is δ absolute in its log.  For the 2^20-entry row of 512 pieces this is ≈ 1.4e-5
+    (+ 4ε·|lse|) in fp32, where the term-count form allows 0.25; short groups keep the term-count form."""
+    lse_ref = np.asarray(lse_ref, dtype=np.float64)
+    k = np.asarray(k, dtype=np.float64)
+    p = np.asarray(n_pieces, dtype=np.float64)
+    by_count = 2 * k + 8
+    by_depth = lane_max + 6 + 3 * (np.ceil(p / wave) + 6) + 2 + np.log1p(k) + 8
+    return np.minimum(by_count, by_depth) * eps + 4 * eps * np.abs(lse_ref)
+
+
 def group_lse_grad(ptr, vals, g, lse):
     """g[grp(k)] · exp(v[k] − lse[grp(k)]) in float64."""
     ptr = np.asarray(ptr, dtype=np.int64)

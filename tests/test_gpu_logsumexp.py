@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import _lse_cases
 import _lse_ref
 
 pytestmark = pytest.mark.gpu
@@ -98,11 +99,12 @@ def _c2_pattern():
     return crow, col
 
 
-def _bound(lse_ref, k):
-    """|fp32 result − fp64 value| ≤ (2k + 8)·ε + 4ε·|lse| for a group of k exp terms (k sums of rounded exp terms and the
-    rescaling of partials: ≤ 2k roundings of relative ε on a total that is ≥ 1 after the shift, the log and the shift add
-    a few ε, and the shift itself is exact up to 4ε·|lse|)."""
-    return (2 * k + 8) * EPS32 + 4 * EPS32 * np.abs(lse_ref)
+def _bound(lse_ref, k, ptr):
+    """|fp32 result − fp64 value| for a group of k exp terms: _lse_ref.fwd_bound, the smaller of (2k + 8)·ε + 4ε·|lse| (k sums of
+    rounded exp terms and the rescaling of partials: ≤ 2k roundings of relative ε on a total that is ≥ 1 after the shift, the
+    log and the shift add a few ε, and the shift itself is exact up to 4ε·|lse|) and the reduction-depth form over the
+    group's range pieces."""
+    return _lse_ref.fwd_bound(lse_ref, k, _lse_cases.pieces(ptr, _lse_cases.range_len("float32")), EPS32)
 
 
 def _check_full(crow, col, val, n_rows, n_cols, include_zeros):
@@ -117,12 +119,12 @@ def _check_full(crow, col, val, n_rows, n_cols, include_zeros):
     order = np.argsort(col_np, kind="stable")
     tptr = np.concatenate([[0], np.cumsum(np.bincount(col_np, minlength=n_cols))])
     lc, kc = _lse_ref.group_lse(tptr, v64[order], n_rows if include_zeros else None)
-    for got, ref, k in ((r, lr, kr), (c, lc, kc)):
+    for got, ref, k, ptr in ((r, lr, kr, crow_np), (c, lc, kc, tptr)):
         got = got.detach().cpu().numpy().astype(np.float64)
         fin = np.isfinite(ref)
         assert np.array_equal(np.isfinite(got), fin) and np.array_equal(got[~fin], ref[~fin])
         err = np.abs(got[fin] - ref[fin])
-        assert (err <= _bound(ref[fin], k[fin])).all(), float(err.max())
+        assert (err <= _bound(ref, k, ptr)[fin]).all(), float(err.max())
     # gradient: per entry Σ_dir g·exp(v − lse); the fp32 exp of a difference of size ≤ |lse| carries ≤ (|v| + |lse| + 2)·2ε relative
     grad_ref = _lse_ref.group_lse_grad(crow_np, v64, gr.numpy(), lr)
     gcol = np.empty_like(v64)
