@@ -43,7 +43,7 @@ t("_ops.spmm", lambda: _ops.spmm(plan, val, Bd))
 t("_ops._lattice_cfg", lambda: _ops._lattice_cfg(plan, be.LAT_SPMM, Bd))
 got = _ops._lattice_cfg(plan, be.LAT_SPMM, Bd)
 t("be.csr_spmm_lattice", lambda: be.csr_spmm_lattice(got[0], got[1], val, Bd))
-t("_ops._lattice_backward", lambda: _ops._lattice_backward(plan, val, G, Bd))
+t("_ops.mm_backward", lambda: _ops.mm_backward(plan, val, G, Bd))
 t("torch.sparse_csr_tensor(crow, col, v)", lambda: torch.sparse_csr_tensor(crow, col, val, (n, n)))
 t("torch.empty((n, 32))", lambda: torch.empty((n, 32), device=dev))
 t("torch.cuda.current_stream(dev).cuda_stream", lambda: torch.cuda.current_stream(dev).cuda_stream)

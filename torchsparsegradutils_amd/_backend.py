@@ -517,19 +517,28 @@ def lattice_lds_bytes(mode: int, vtype: int, p: int, ty: int, tz: int, ry: int, 
     return int(load_library().tsgu_lattice_lds_bytes(mode, vtype, p, ty, tz, ry, rz, nloc, recw, threads, ring, cpl))
 
 
+_LATTICE_ELEMENT_BYTES = {torch.float32: 4, torch.bfloat16: 2, torch.float64: 8}
+
+
+def lattice_rows_fit(mode: int, dtype: torch.dtype, p: int, stored_order: bool = True) -> bool:
+    """Are the sweeps compiled for dense rows of p `dtype` values: whole 16-byte lanes, 1, 2, 4, 8 or 16 of them — one lane per row
+    (4 fp32 columns) for the product in the stored order (`stored_order`: the walked plan is not the transposed one) only."""
+    es = _LATTICE_ELEMENT_BYTES.get(dtype)
+    if es is None or (p * es) % 16:
+        return False
+    lanes = (p * es) // 16
+    return lanes in (2, 4, 8, 16) or (lanes == 1 and mode == LAT_SPMM and dtype == torch.float32 and stored_order)
+
+
 def lattice_config(lp, mode: int, dtype: torch.dtype, p: int):
     """Launch configuration (tile, segments, record tables) of the _lattice.LatticePlan `lp` for these operands, or None."""
     from . import _lattice
 
-    if dtype not in (torch.float32, torch.bfloat16, torch.float64):
+    if not lattice_rows_fit(mode, dtype, p, lp.kind == 0):
         return None
-    es = {torch.float32: 4, torch.bfloat16: 2, torch.float64: 8}[dtype]
-    lanes = (p * es) // 16
-    if (p * es) % 16 or lanes not in (1, 2, 4, 8, 16) or (lanes == 1 and not (mode == LAT_SPMM and dtype == torch.float32 and lp.kind == 0)):
-        return None      # (one lane per row — 4 fp32 columns — is compiled for the stored-order product only)
     import sys
 
-    return _lattice.config_for(lp, mode, _VTYPE[dtype], p, es, lattice_lds_bytes, be=sys.modules[__name__])
+    return _lattice.config_for(lp, mode, _VTYPE[dtype], p, _LATTICE_ELEMENT_BYTES[dtype], lattice_lds_bytes, be=sys.modules[__name__])
 
 
 def lattice_tune(lp, mode: int, dtype: torch.dtype, p: int, time_ms):
@@ -538,8 +547,7 @@ def lattice_tune(lp, mode: int, dtype: torch.dtype, p: int, time_ms):
 
     from . import _lattice
 
-    es = {torch.float32: 4, torch.bfloat16: 2, torch.float64: 8}[dtype]
-    return _lattice.tune_config(lp, mode, _VTYPE[dtype], p, es, lattice_lds_bytes, sys.modules[__name__], time_ms)
+    return _lattice.tune_config(lp, mode, _VTYPE[dtype], p, _LATTICE_ELEMENT_BYTES[dtype], lattice_lds_bytes, sys.modules[__name__], time_ms)
 
 
 def lattice_rows(crow, col, dims, status, slot, thash=None, trep=None, remap=None, ctable=None, lens=None, rcls=None, disp=None,

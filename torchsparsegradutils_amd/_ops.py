@@ -1,16 +1,16 @@
-"""Kernel selection for one sparse operand: row-pair union kernels when neighbouring rows share columns (stencils,
-banded factors, meshes) and the operands qualify, plain gather kernels otherwise.  Both produce the same values
-(same per-row summation order when a pair has one entry lane, except that brick plans of 3-D lattices sum a row of the
-transposed product plane by plane: equal to rounding); the choice is speed only.
+"""Kernel selection for one sparse operand.  Each product of a step — the forward, the transposed forward, the SDDMM and the
+fused backward — runs on the first kernel family that the pattern and the operands qualify for, in one order of preference written
+once, in `_choose`: lattice sweep / plane march (stencils on a row-major lattice), row-block tiles, row pairs (neighbouring rows
+share columns: meshes, banded factors), plain gather kernels otherwise.  The families compute the same products (up to the
+summation order each kernel documents); the choice is speed only.
 
-Batched CSR operands (torch layout, equal nnz per item) that qualify for the row-pair kernels are handed to them as
-ONE block-diagonal 2-D problem (`_pattern.flat_of`: two vectorised adds on the index arrays, values untouched):
-the row-pair plans are translation-deduplicated, so items that share a pattern also share their plan records."""
+Batched CSR operands (torch layout, equal nnz per item) that qualify for a planned family are handed to it as ONE block-diagonal
+2-D problem (`_pattern.flat_of`: two vectorised adds on the index arrays, values untouched): the row-pair plans are
+translation-deduplicated, so items that share a pattern also share their plan records."""
 
 from __future__ import annotations
 
 import os
-import threading
 
 import torch
 
@@ -56,20 +56,12 @@ TUNE_COLD = os.environ.get("TSGU_TUNE_COLD", "1") != "0"
 
 
 # ---- what a step launched ----------------------------------------------------------------------------------------------------------
-# The order of preference between the kernel families (lattice -> batched row pairs -> row-block tiles -> row pairs -> plan-free) is
-# written down ONCE, in spmm() / mm_backward() below.  The step's C++ host path (sparse_matmul._settle_step_plan) does not decide
-# anything a second time: the entry points NOTE what they launched — family and the plan objects — with the pattern, and the host
-# path is derived from notes that have stopped changing.  (Round 5 re-derived the decision there and a finished-but-unclaimed
-# row-pair future kept every tile pattern off the C++ path.)
-_CHOICE = threading.local()
+# The step's C++ host path (sparse_matmul._settle_step_plan) does not decide anything a second time: the entry points below NOTE what
+# they launched — family and the plan objects — with the pattern, and the host path is derived from notes that have stopped changing.
+# (Round 5 re-derived the decision there and a finished-but-unclaimed row-pair future kept every tile pattern off the C++ path.)
 
 
-def _chose(family: str, *payload) -> None:
-    """What the product that is about to be launched runs on (read by mm_backward_separate right after the call, same thread)."""
-    _CHOICE.last = (family, payload)
-
-
-def _note(plan: RowGather, product: str, dense: torch.Tensor, family: str, *payload) -> None:
+def _note(plan: RowGather, product: str, dense: torch.Tensor, family: str, payload: tuple) -> None:
     own = plan.core.own
     sig = (dense.dtype, dense.size(-1))          # a pattern may be used with operands of several types and widths: a note is about ONE
     prev = own.get("launched_" + product)
@@ -145,10 +137,8 @@ def _lattice_cfg(plan: RowGather, mode: int, dense: torch.Tensor, *others: torch
         return None
     if dense.dtype not in LATTICE_DTYPES:
         return None
-    row_bytes = dense.size(-1) * dense.element_size()
-    lanes = row_bytes // 16
     wide = dense.dtype == torch.float32 and dense.size(-1) > 64 and dense.size(-1) % 64 == 0     # plane march only: column tiles of 64
-    if not wide and (row_bytes % 16 or lanes not in (1, 2, 4, 8, 16) or (lanes == 1 and not (mode == _be.LAT_SPMM and dense.dtype == torch.float32))):
+    if not wide and not _be.lattice_rows_fit(mode, dense.dtype, dense.size(-1)):
         return None            # dense rows the sweeps are not compiled for: do not even analyse the pattern
     fwd = _lattice_plan(plan)
     if fwd is None:
@@ -294,150 +284,138 @@ def _tile_for(plan: RowGather, dense: torch.Tensor, *others: torch.Tensor):
     return plan.tile_plan(geo)
 
 
-def _flat(plan: RowGather, *dense: torch.Tensor):
-    """(block-diagonal 2-D plan, flattened dense operands) of a batched problem, or None when the operands are not
-    batch-contiguous (the plain kernels then take the batch as gridDim.y)."""
-    if plan.batch is None or any(t.dim() != 3 for t in dense):
-        return None
-    flat = []
-    for t in dense:
+# ---- which family a product runs on ------------------------------------------------------------------------------------------------
+# A step is made of up to four products: the forward A·B (FWD), the transposed forward Aᵀ·G on the transposed pattern with A's own
+# values (FWD_T), the SDDMM at A's stored entries (SDDMM) and the fused backward, both gradients in one walk (BWD).  _choose() walks
+# the order of preference between the kernel families once for all of them — lattice sweep / plane march -> row-block tiles -> row
+# pairs -> plan-free — and the entry points below only note, launch and reshape what it returns.
+FWD, FWD_T, SDDMM, BWD = 0, 1, 2, 3
+LATTICE, TILES, ROW_PAIRS, PLAN_FREE = "lattice", "tiles", "row pairs", "plan-free"
+_SWEEP = (_be.LAT_SPMM, _be.LAT_SPMMT, _be.LAT_SDDMM)        # the lattice mode of FWD, FWD_T and SDDMM
+
+
+def _flat(x: torch.Tensor, y: torch.Tensor = None):
+    """[x, y] of a batched problem as the operands of its block-diagonal 2-D form (`_pattern.flat_of`), or None when they are not
+    batch-contiguous (the plain kernels then take the batch as gridDim.y).  y may be None."""
+    out = [None, None]
+    for i, t in enumerate((x, y)):
+        if t is None:
+            continue
+        if t.dim() != 3:
+            return None
         t = _be.rowmajor(t)
         if t.size(0) > 1 and t.stride(0) != t.size(1) * t.stride(1):
             return None
         if t.size(1) > 1 and t.stride(1) != t.size(2):
             return None
-        flat.append(t.reshape(-1, t.size(-1)))
-    return _pt.flat_of(plan), flat
+        out[i] = t.reshape(-1, t.size(-1))
+    return out
 
 
-def _lattice_backward(plan: RowGather, values: torch.Tensor, G: torch.Tensor, B: torch.Tensor):
-    """Both gradients of C = A·B by two plane sweeps: the SDDMM in A's stored order (gradA leaves fully coalesced) and
-    Aᵀ·G on the transposed pattern with the values read from A's own array.  None when the pattern is not a lattice."""
-    if plan.perm is not None:
-        return None
-    fplan, Gf, Bf = plan, G, B
-    if plan.batch is not None:
-        fl = _flat(plan, G, B)
-        if fl is None:
-            return None
-        fplan, (Gf, Bf) = fl
-    vals = values.reshape(-1)
-    fwd = _lattice_cfg(fplan, _be.LAT_SDDMM, Bf, Gf)
-    if fwd is None:
-        return None
-    bwd = _lattice_cfg(fplan, _be.LAT_SPMMT, Gf)
-    if bwd is None:
-        return None
-    ga = _be.csr_sddmm_lattice(fwd[0], fwd[1], Gf, Bf)
-    gb = _be.csr_spmm_lattice(bwd[0], bwd[1], vals, Gf)
-    _note(plan, "bwd", G, "lattice", fwd[0], fwd[1], bwd[0], bwd[1])
-    return ga.view(values.shape), gb.view(B.shape)
+def _choose(product: int, plan: RowGather, dtype: torch.dtype, x: torch.Tensor, y: torch.Tensor = None, asks: int = 1):
+    """(family, payload, walked plan, x, y) of one product on GPU operands.
 
+    `plan` is the pattern the values are stored in (FWD_T walks its transposed pattern), `dtype` the values' type (SDDMM: G's), x and
+    y the dense operands in the order the plans take them — FWD: B; FWD_T: G; SDDMM: the gathered operand, the row operand; BWD: B, G.
+    Batched operands come back flattened, and the walked plan is then the block-diagonal one.  The payload is what the launch reads
+    and what is noted: (lattice plan, configuration) per sweep, the tile plan(s), the row-pair plan; plan-free: the transposed pattern
+    when the product walks it.
 
-def mm_backward(plan: RowGather, values: torch.Tensor, G: torch.Tensor, B: torch.Tensor):
-    """(gradA values in A's order, gradB) of C = A·B in one pass over the transposed pattern."""
-    if not G.is_cuda:       # CPU operands: the torch-op path (_cpu.py), chosen by the operands' device and nothing else
-        return _cpu.sddmm(plan, G, B), _cpu.spmm(plan.transposed, values, G)
-    same = values.dtype == G.dtype == B.dtype
-    if same and ENABLE_LATTICE and values.dtype in LATTICE_DTYPES:
-        got = _lattice_backward(plan, values, G, B)
-        if got is not None:
-            return got
-    if same and plan.batch is not None and plan.perm is None and ENABLE_TILE and _be.tile_geometry(B.dtype, B.size(-1)) is not None:
-        # batched operands whose items are meshes: the block-diagonal problem on the row-block tiles (round 6; the tile plan of a
-        # block-diagonal pattern is the items' plans one after the other — a block of 64 rows never spans two items' columns unless
-        # n is not a multiple of 64, and then its tile simply lists both)
-        fl = _flat(plan, G, B)
-        if fl is not None:
-            fplan, (Gf, Bf) = fl
-            tp, tt = _tile_for(fplan, Bf, Gf), _tile_for(fplan.transposed, Gf)
+    Asking has side effects, so which plans are asked for, on which pattern and in which order is part of the behaviour: _tile_for and
+    _pack_for count a use of the pattern and may start a plan build, _lattice_plan counts a sighting of a volatile pattern.  `asks`:
+    how often FWD_T asks for its sweep (spmm_t asks twice: the step at which a volatile pattern first runs on the lattice counts on it)."""
+    batched = plan.batch is not None
+    ok = x.dtype == dtype and (y is None or y.dtype == dtype)
+    if product == SDDMM:
+        ok = ok and plan.perm is None and not batched           # (no batched SDDMM)
+    elif product != BWD:
+        ok = ok and not _be.is_transposed_view(x)               # (transposed views: the plan-free kernel reads them column-strided)
+    xf, yf = x, y
+    if ok and batched:
+        flat = _flat(x, y)
+        ok = flat is not None
+        if ok:
+            xf, yf = flat
+    # lattice sweeps / plane march: the stored-order pattern (FWD_T walks it transposed, through the same plan)
+    if ok and ENABLE_LATTICE and plan.perm is None and dtype in LATTICE_DTYPES:
+        src = _pt.flat_of(plan) if batched else plan
+        if product == BWD:
+            got = _lattice_cfg(src, _be.LAT_SDDMM, xf, yf)
+            if got is not None:
+                t = _lattice_cfg(src, _be.LAT_SPMMT, yf)
+                if t is not None:
+                    return LATTICE, got + t, src, xf, yf
+        else:
+            mode = _SWEEP[product]
+            got = _lattice_cfg(src, mode, xf) if yf is None else _lattice_cfg(src, mode, xf, yf)
+            if got is None and asks > 1:
+                got = _lattice_cfg(src, mode, xf)
+            if got is not None:
+                return LATTICE, got, src, xf, yf
+    if product == FWD_T:
+        plan = plan.transposed
+    # row-block tiles: a batched problem (its block-diagonal form) and the fused backward need the stored order
+    if ok and (plan.perm is None or not (batched or product == BWD)) and (
+            not batched or (ENABLE_TILE and _be.tile_geometry(dtype, x.size(-1)) is not None)):
+        src = _pt.flat_of(plan) if batched else plan
+        tp = _tile_for(src, xf) if yf is None else _tile_for(src, xf, yf)
+        if product == BWD:
+            tt = _tile_for(src.transposed, yf)         # (both plans are asked for before either is tested)
             if tp is not None and tt is not None:
-                _note(plan, "bwd", G, "tiles", tp, tt)
-                ga, gb = _be.csr_sddmm_tile(tp, Gf, Bf), _be.csr_spmm_tile(tt, values.reshape(-1), Gf)
-                return ga.view(values.shape), gb.view(B.shape)
-    if same and plan.batch is not None and ENABLE_PACK:
-        fl = _flat(plan, G, B)
-        if fl is not None:
-            fplan, (Gf, Bf) = fl
-            rp = _pack_for(fplan.transposed, Gf, Bf)
-            if rp is not None:
-                ga, gb = _be.csr_mm_backward_rowpack(fplan.transposed.crow, rp, values.reshape(-1), Gf, Bf, fplan.n_cols)
-                _note(plan, "bwd", G, "row pairs", rp)
-                return ga.view(values.shape), gb.view(B.shape)
-    t = plan.transposed
-    if same and plan.batch is None and plan.perm is None:
-        # row-block tiles: the SDDMM in stored order + the transposed product on the transposed pattern's tiles (A's own values)
-        tp, tt = _tile_for(plan, B, G), _tile_for(t, G)
-        if tp is not None and tt is not None:
-            _note(plan, "bwd", G, "tiles", tp, tt)
-            return _be.csr_sddmm_tile(tp, G, B), _be.csr_spmm_tile(tt, values, G)
-    rp = _pack_for(t, G, B) if same else None
-    if rp is not None and rp.srcstart is not None and plan.batch is None and plan.perm is None:
-        # the transposed plan reached the dictionary form through row-relative value positions (mesh orderings): the SDDMM on the
-        # stored-order plan + the transposed product beat the fused walk (mesh27_blocked: 124 + 208 us against 417 us)
-        _note(plan, "bwd", G, "row pairs", rp)
-        return sddmm(plan, G, B), spmm(t, values, G, owner=plan)
-    if rp is not None:
-        _note(plan, "bwd", G, "row pairs", rp)
-        return _be.csr_mm_backward_rowpack(t.crow, rp, values, G, B, t.n_rows)
-    _note(plan, "bwd", G, "plan-free", t)
-    return _be.csr_mm_backward(t, values, G, B, plan.n_rows, plan.n_cols)
+                return TILES, (tp, tt), src, xf, yf
+        elif tp is not None:
+            return TILES, (tp,), src, xf, yf
+    # row pairs (the fused backward walks the transposed pattern; the SDDMM only ownership-bit records, one entry lane per pair)
+    if ok and (not batched or ENABLE_PACK):
+        src = _pt.flat_of(plan) if batched else plan
+        if product == BWD:
+            src = src.transposed
+            rp = _pack_for(src, yf, xf)
+        elif product == SDDMM:
+            rp = _pack_for(src, xf, yf, need_plain_slots=True)
+            rp = rp if rp is not None and rp.upos is None else None
+        else:
+            rp = _pack_for(src, xf)
+        if rp is not None:
+            return ROW_PAIRS, (rp,), src, xf, yf
+    if product == BWD:
+        plan = plan.transposed
+    return PLAN_FREE, (plan,) if product == FWD_T or product == BWD else (), plan, x, y
 
 
-def spmm(plan: RowGather, values: torch.Tensor, B: torch.Tensor, owner: RowGather = None) -> torch.Tensor:
-    """A·B for the operand described by (plan, values); perm-aware (transposed / un-coalesced plans).  `owner`: when
-    `plan` is `owner.transposed`, the pattern whose stored order the values are in (lets Aᵀ·G take the lattice sweep)."""
+def _spmm_launch(choice, values: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """Launch a chosen FWD / FWD_T product; `B` is the caller's operand (choice[3] its flattened form for a batched problem)."""
+    family, payload, src, Bf, _ = choice
+    if family is PLAN_FREE:
+        return _be.csr_spmm(src.crow, src.col, values, B, src.n_rows, src.n_cols, perm=src.perm, max_row_nnz=src.max_row_nnz)
+    vals = values if Bf is B else values.reshape(-1)
+    if family is LATTICE:
+        out = _be.csr_spmm_lattice(payload[0], payload[1], vals, Bf)
+    elif family is TILES:
+        out = _be.csr_spmm_tile(payload[0], vals, Bf)
+    else:
+        out = _be.csr_spmm_rowpack(src.crow, vals, payload[0], Bf, src.n_rows)
+    return out if Bf is B else out.view(B.size(0), -1, B.size(-1))
+
+
+def _sddmm_launch(choice, plan: RowGather, G: torch.Tensor, B: torch.Tensor, alpha: float = 1.0, swap_roles: bool = False):
+    family, payload, _, gathered, rowop = choice
+    if family is LATTICE:
+        return _be.csr_sddmm_lattice(payload[0], payload[1], rowop, gathered, alpha=alpha)
+    if family is TILES:
+        return _be.csr_sddmm_tile(payload[0], rowop, gathered, alpha=alpha)
+    if family is ROW_PAIRS:
+        return _be.csr_sddmm_rowpack(plan.crow, payload[0], rowop, gathered, plan.n_rows, alpha=alpha)
+    return _be.csr_sddmm(plan.crow, plan.col, G, B, plan.n_rows, plan.n_cols, alpha=alpha, swap_roles=swap_roles)
+
+
+def spmm(plan: RowGather, values: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """A·B for the operand described by (plan, values); perm-aware (transposed / un-coalesced plans)."""
     if not B.is_cuda:
         return _cpu.spmm(plan, values, B)
-    if values.dtype == B.dtype and not _be.is_transposed_view(B):  # transposed views: zero-copy column-strided K1
-        stored = plan.perm is None
-        if ENABLE_LATTICE and (stored or (owner is not None and owner.perm is None)):
-            src = plan if stored else owner
-            fsrc, Bf = src, B
-            if src.batch is not None:
-                fl = _flat(src, B)
-                fsrc, Bf = (fl[0], fl[1][0]) if fl is not None else (None, None)
-            got = None
-            if fsrc is not None:
-                got = _lattice_cfg(fsrc, _be.LAT_SPMM if stored else _be.LAT_SPMMT, Bf)
-            if got is not None:
-                out = _be.csr_spmm_lattice(got[0], got[1], values.reshape(-1), Bf)
-                _chose("lattice", got[0], got[1])
-                if stored:
-                    _note(plan, "fwd", B, "lattice", got[0], got[1])
-                return out.view(B.shape[:-2] + (plan.n_rows, B.size(-1)))
-        if plan.batch is not None and stored and ENABLE_TILE and _be.tile_geometry(B.dtype, B.size(-1)) is not None:
-            fl = _flat(plan, B)
-            if fl is not None:
-                fplan, (Bf,) = fl
-                tp = _tile_for(fplan, Bf)
-                if tp is not None:
-                    _chose("tiles", tp)
-                    _note(plan, "fwd", B, "tiles", tp)
-                    return _be.csr_spmm_tile(tp, values.reshape(-1), Bf).view(B.size(0), plan.n_rows, B.size(-1))
-        if plan.batch is not None and ENABLE_PACK:
-            fl = _flat(plan, B)
-            if fl is not None:
-                fplan, (Bf,) = fl
-                rp = _pack_for(fplan, Bf)
-                if rp is not None:
-                    out = _be.csr_spmm_rowpack(fplan.crow, values.reshape(-1), rp, Bf, fplan.n_rows)
-                    _chose("row pairs", rp)
-                    _note(plan, "fwd", B, "row pairs", rp)
-                    return out.view(B.size(0), plan.n_rows, B.size(-1))
-        tp = _tile_for(plan, B)
-        if tp is not None:
-            _chose("tiles", tp)
-            _note(plan, "fwd", B, "tiles", tp)
-            return _be.csr_spmm_tile(tp, values, B)
-        rp = _pack_for(plan, B)
-        if rp is not None:
-            _chose("row pairs", rp)
-            _note(plan, "fwd", B, "row pairs", rp)
-            return _be.csr_spmm_rowpack(plan.crow, values, rp, B, plan.n_rows)
-    _chose("plan-free", plan)
-    _note(plan, "fwd", B, "plan-free")
-    return _be.csr_spmm(plan.crow, plan.col, values, B, plan.n_rows, plan.n_cols, perm=plan.perm, max_row_nnz=plan.max_row_nnz)
+    choice = _choose(FWD, plan, values.dtype, B)
+    _note(plan, "fwd", B, choice[0], choice[1])
+    return _spmm_launch(choice, values, B)
 
 
 def spmm_t(owner: RowGather, values: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
@@ -445,49 +423,50 @@ def spmm_t(owner: RowGather, values: torch.Tensor, G: torch.Tensor) -> torch.Ten
     everything else goes through the cached transposed pattern (built on first use)."""
     if not G.is_cuda:
         return _cpu.spmm(owner.transposed, values, G)
-    if ENABLE_LATTICE and owner.perm is None and values.dtype == G.dtype and not _be.is_transposed_view(G):
-        fsrc, Gf = owner, G
-        if owner.batch is not None:
-            fl = _flat(owner, G)
-            fsrc, Gf = (fl[0], fl[1][0]) if fl is not None else (None, None)
-        got = _lattice_cfg(fsrc, _be.LAT_SPMMT, Gf) if fsrc is not None else None
-        if got is not None:
-            out = _be.csr_spmm_lattice(got[0], got[1], values.reshape(-1), Gf)
-            _chose("lattice", got[0], got[1])
-            return out.view(G.shape[:-2] + (owner.n_cols, G.size(-1)))
-    return spmm(owner.transposed, values, G, owner=owner)
+    return _spmm_launch(_choose(FWD_T, owner, values.dtype, G, asks=2), values, G)
 
 
 def sddmm(plan: RowGather, G: torch.Tensor, B: torch.Tensor, alpha: float = 1.0, swap_roles: bool = False) -> torch.Tensor:
     """alpha·<G[row k], B[col k]> (or roles swapped) at the plan's stored entries, in plan order."""
     if not G.is_cuda:
         return _cpu.sddmm(plan, G, B, alpha=alpha, swap_roles=swap_roles)
-    gathered = G if swap_roles else B
-    rowop = B if swap_roles else G
-    if plan.perm is None and G.dtype == B.dtype:
-        got = _lattice_cfg(plan, _be.LAT_SDDMM, gathered, rowop)
-        if got is not None:
-            _chose("lattice", got[0], got[1])
-            return _be.csr_sddmm_lattice(got[0], got[1], rowop, gathered, alpha=alpha)
-        tp = _tile_for(plan, gathered, rowop)
-        if tp is not None:
-            _chose("tiles", tp)
-            return _be.csr_sddmm_tile(tp, rowop, gathered, alpha=alpha)
-        rp = _pack_for(plan, gathered, rowop, need_plain_slots=True)
-        if rp is not None and rp.upos is None:
-            _chose("row pairs", rp)
-            return _be.csr_sddmm_rowpack(plan.crow, rp, rowop, gathered, plan.n_rows, alpha=alpha)
-    _chose("plan-free")
-    return _be.csr_sddmm(plan.crow, plan.col, G, B, plan.n_rows, plan.n_cols, alpha=alpha, swap_roles=swap_roles)
+    choice = _choose(SDDMM, plan, G.dtype, G if swap_roles else B, B if swap_roles else G)
+    return _sddmm_launch(choice, plan, G, B, alpha, swap_roles)
+
+
+def mm_backward(plan: RowGather, values: torch.Tensor, G: torch.Tensor, B: torch.Tensor):
+    """(gradA values in A's order, gradB) of C = A·B in one pass over the transposed pattern."""
+    if not G.is_cuda:       # CPU operands: the torch-op path (_cpu.py), chosen by the operands' device and nothing else
+        return _cpu.sddmm(plan, G, B), _cpu.spmm(plan.transposed, values, G)
+    family, payload, src, Bf, Gf = _choose(BWD, plan, values.dtype, B, G)
+    _note(plan, "bwd", G, family, payload)
+    vals = values if Bf is B else values.reshape(-1)
+    if family is LATTICE:
+        # the SDDMM in A's stored order (gradA leaves fully coalesced) and Aᵀ·G on the transposed walk of the same plan
+        ga, gb = _be.csr_sddmm_lattice(payload[0], payload[1], Gf, Bf), _be.csr_spmm_lattice(payload[2], payload[3], vals, Gf)
+    elif family is TILES:
+        # the SDDMM on the stored pattern's tiles + the transposed product on the transposed pattern's tiles (A's own values)
+        ga, gb = _be.csr_sddmm_tile(payload[0], Gf, Bf), _be.csr_spmm_tile(payload[1], vals, Gf)
+    elif family is ROW_PAIRS and payload[0].srcstart is not None and plan.batch is None and plan.perm is None:
+        # the transposed plan reached the dictionary form through row-relative value positions (mesh orderings): the SDDMM on the
+        # stored-order plan + the transposed product beat the fused walk (mesh27_blocked: 124 + 208 us against 417 us)
+        return sddmm(plan, G, B), _spmm_launch(_choose(FWD_T, plan, values.dtype, G), values, G)
+    elif family is ROW_PAIRS:
+        ga, gb = _be.csr_mm_backward_rowpack(src.crow, payload[0], vals, Gf, Bf, src.n_rows)
+    else:
+        return _be.csr_mm_backward(src, values, G, B, plan.n_rows, plan.n_cols)
+    return (ga, gb) if Bf is B else (ga.view(values.shape), gb.view(B.shape))
 
 
 def mm_backward_separate(plan: RowGather, values: torch.Tensor, G: torch.Tensor, B: torch.Tensor):
     """(gradA values in A's order, gradB) as TWO products — the SDDMM in stored order and Aᵀ·G — for operands the fused walk is not
     compiled for (fp64, very wide rows).  Noted like mm_backward when both products ran on the same family."""
-    ga = sddmm(plan, G, B)
-    a = getattr(_CHOICE, "last", None)
-    gb = spmm_t(plan, values, G)
-    b = getattr(_CHOICE, "last", None)
-    if G.is_cuda and a is not None and b is not None and a[0] == b[0]:
-        _note(plan, "bwd", G, a[0], *(a[1] + b[1]))
+    if not G.is_cuda:
+        return sddmm(plan, G, B), spmm_t(plan, values, G)
+    a = _choose(SDDMM, plan, G.dtype, B, G)
+    ga = _sddmm_launch(a, plan, G, B)
+    b = _choose(FWD_T, plan, values.dtype, G, asks=2)
+    gb = _spmm_launch(b, values, G)
+    if a[0] is b[0]:
+        _note(plan, "bwd", G, a[0], a[1] + b[1])
     return ga, gb
