@@ -673,6 +673,46 @@ int tsgu_segment_logsumexp_backward(int vtype, int itype, int64_t nnz, const voi
                                     const void* g_grp, const void* lse_grp, const void* idx, const void* g_idx,
                                     const void* lse_idx, void* grad, int device, void* stream);
 
+/*
+ * Segmented and gathered dense products (segment_mm / gather_mm and their gradients).
+ * replaces: the tensor_split / nested-tensor matmul / cat of     torchsparsegradutils/indexed_matmul.py:95-105 (segment_mm),
+ *           the R boolean masks / nested matmul / scatter of     indexed_matmul.py:203-217 (gather_mm),
+ *           and the nested-tensor backward autograd takes through both.
+ *
+ * Rows are grouped by a plan of n_seg + 3 words each (built with device ops, indexed_matmul.py):
+ *   offsets:  0 = offsets[0] <= offsets[1] <= ... <= offsets[n_seg + 1] <= offsets[n_seg + 2] = n.  Rows (positions in
+ *             perm order) [offsets[r + 1], offsets[r + 2]) use b[r]; rows before offsets[1] and from offsets[n_seg + 1] on
+ *             had an index outside [0, n_seg) and are written as zeros.
+ *   tile_ptr: tile_ptr[e] = sum over e' < e of ceil((offsets[e' + 1] - offsets[e']) / tsgu_segment_mm_tile_rows()).
+ * perm (itype, may be NULL = identity) maps a position to its row of a and out.  One workgroup per row tile: the launch takes
+ * max_tiles >= ceil(n / BM) + min(n_seg, n) + 2 workgroups (a bound of tile_ptr[n_seg + 2]; no read-back), surplus ones exit.
+ *
+ * Forward (and grad_a, with b given as a transposed view):  out[perm[i]][:] = a[perm[i]][:] @ b[r]   (i in segment r)
+ *   a: (n, d1), row stride lda;  b[r][k][j] at b + r*b_stride0 + k*b_stride1 + j*b_stride2, b_stride1 or b_stride2 == 1;
+ *   out: (n, d2), row stride ldo.  MFMA (f32 16x16x4, f64 16x16x4, bf16 16x16x32 with fp32 accumulation and one rounding).
+ *   f32 / f64 results are the k-ordered fma chain a[i][0]*b[0][j] + ... over k = 0 .. d1 - 1.
+ */
+int tsgu_segment_mm_tile_rows(void);
+int tsgu_segment_mm(int vtype, int itype, int64_t n, int64_t d1, int64_t d2, int64_t n_seg, const void* offsets,
+                    const void* tile_ptr, int64_t max_tiles, const void* perm, const void* a, int64_t lda, const void* b,
+                    int64_t b_stride0, int64_t b_stride1, int64_t b_stride2, void* out, int64_t ldo, int device, void* stream);
+/*
+ * grad_b[r] = sum over the rows i of segment r of a[perm[i]]ᵀ g[perm[i]]   (the b-gradient of both products, replacing the
+ * nested-tensor backward of indexed_matmul.py:95-105 / :203-217).  grad_b: (n_seg, d1, d2) contiguous, in b's dtype.
+ * Split-K: each segment's rows are cut into chunks of chunk_rows (a function of the shapes only); one workgroup per
+ * (chunk, 64 x 64 output tile) sums its rows in order.  A segment of one chunk is written directly; longer ones leave fp32
+ * (fp64 for fp64) partials that a second kernel sums in chunk order; empty segments get zeros.  No atomics: bit-identical
+ * from call to call.  chunk_ptr[n_seg + 1] is the chunk prefix of the real segments (sum of ceil(len_r / chunk_rows)) and
+ * part_ptr[n_seg + 1] the prefix of the partial slots (chunk counts of segments with two or more chunks).
+ * tsgu_segment_mm_grad_b_workspace gives chunk_rows, the launch bound max_chunks and the workspace bytes (16-byte aligned).
+ */
+int tsgu_segment_mm_grad_b_workspace(int vtype, int64_t n, int64_t n_seg, int64_t d1, int64_t d2, int64_t* chunk_rows,
+                                     int64_t* max_chunks, int64_t* bytes);
+int tsgu_segment_mm_grad_b(int vtype, int itype, int64_t n, int64_t d1, int64_t d2, int64_t n_seg, const void* offsets,
+                           const void* chunk_ptr, const void* part_ptr, int64_t chunk_rows, int64_t max_chunks, const void* perm,
+                           const void* a, int64_t lda, const void* g, int64_t ldg, void* grad_b, void* workspace,
+                           int64_t workspace_bytes, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

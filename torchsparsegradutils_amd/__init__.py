@@ -1,13 +1,14 @@
 """MI355X-native (gfx950) implementation of torchsparsegradutils' sparse hot path.
 
-Drop-in names for ``sparse_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` / ``sparse_logsumexp`` /
-``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``); the arithmetic runs in hand-written HIP
-kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
+Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
+``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``);
+the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
 from ._backend import poll_errors
 from ._compat import linalg_solve_triangular_compat
 from ._pattern import wait_for_plans
+from .indexed_matmul import GatherMM, SegmentMM, gather_mm, segment_mm
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
@@ -20,6 +21,8 @@ from .sparse_solve import (
 
 __all__ = [
     "sparse_mm",
+    "gather_mm",
+    "segment_mm",
     "sparse_triangular_solve",
     "sparse_generic_solve",
     "sparse_generic_lstsq",
@@ -32,6 +35,8 @@ __all__ = [
     "SparseTriangularSolve",
     "SparseGenericSolve",
     "SparseLogSumExp",
+    "SegmentMM",
+    "GatherMM",
     "linalg_solve_triangular_compat",
 ]
 

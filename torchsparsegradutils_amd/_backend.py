@@ -66,6 +66,17 @@ SIGNATURES = {
     "tsgu_segment_logsumexp_backward": (
         _int, [_int, _int, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr],
     ),
+    "tsgu_segment_mm_tile_rows": (_int, []),
+    "tsgu_segment_mm": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _int, _ptr],
+    ),
+    "tsgu_segment_mm_grad_b_workspace": (
+        _int, [_int, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    ),
+    "tsgu_segment_mm_grad_b": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64,
+               _int, _ptr],
+    ),
     "tsgu_csr_mm_backward": (
         _int,
         [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _ptr, _i64,
@@ -835,6 +846,74 @@ def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx, n_
     return grad
 
 
+SEGMENT_MM_TILE_ROWS = 128       # kImmBM of csrc/indexed_mm_impl.h: the row tile of the plans' tile prefix
+
+
+def segment_mm_grad_b_workspace(dtype: torch.dtype, n: int, n_seg: int, d1: int, d2: int):
+    """(chunk rows, launch bound on chunks, workspace bytes) of tsgu_segment_mm_grad_b: functions of the shapes only."""
+    c, mc, b = _i64(0), _i64(0), _i64(0)
+    check(load_library().tsgu_segment_mm_grad_b_workspace(_VTYPE[dtype], n, n_seg, d1, d2, ctypes.byref(c), ctypes.byref(mc),
+                                                           ctypes.byref(b)), "tsgu_segment_mm_grad_b_workspace")
+    return int(c.value), int(mc.value), int(b.value)
+
+
+def _imm_geometry(plan, *tensors) -> torch.device:
+    lib = load_library()
+    if lib.tsgu_segment_mm_tile_rows() != SEGMENT_MM_TILE_ROWS:
+        raise HipExtensionMissing("libtsgu_hip.so was built with another segment_mm row tile; rebuild the extension")
+    dev = require_device(plan.offsets, plan.perm, *tensors)
+    if plan.perm is not None and plan.perm.dtype != plan.offsets.dtype:
+        raise RuntimeError(f"index dtypes differ: {plan.offsets.dtype} and {plan.perm.dtype}")
+    return dev
+
+
+def segment_mm(plan, a, b, out):
+    """out[perm[i]] = a[perm[i]] @ b[r] for the rows i of plan segment r (zeros outside the real segments).  `a` and `out` are
+    row-major 2-D (n, d1) / (n, d2); `b` (R, d1, d2) with unit stride on one of its two last axes (a transposed view is read
+    in place).  The plan: indexed_matmul._Plan."""
+    dev = _imm_geometry(plan, a, b, out)
+    n, d1 = a.shape
+    d2 = out.size(1)
+    if a.dtype != b.dtype or out.dtype != a.dtype:
+        raise RuntimeError(f"segment_mm: dtypes differ: {a.dtype}, {b.dtype}, {out.dtype}")
+    if a.stride(1) != 1 or out.stride(1) != 1 or b.dim() != 3 or b.size(1) != d1 or b.size(2) != d2:
+        raise RuntimeError("segment_mm: operands of unexpected layout")
+    with torch.cuda.device(dev):
+        check(
+            load_library().tsgu_segment_mm(
+                vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, _p(plan.offsets), _p(plan.tile_ptr), plan.max_tiles,
+                _p(plan.perm), _p(a), max(a.stride(0), d1), _p(b), b.stride(0), b.stride(1), b.stride(2), _p(out),
+                max(out.stride(0), d2), dev.index, _stream(dev),
+            ),
+            "tsgu_segment_mm",
+        )
+    return out
+
+
+def segment_mm_grad_b(plan, a, g, grad_b):
+    """grad_b[r] = Σ over the rows i of plan segment r of a[perm[i]]ᵀ g[perm[i]]; `grad_b` (R, d1, d2) contiguous."""
+    dev = _imm_geometry(plan, a, g, grad_b)
+    n, d1 = a.shape
+    d2 = g.size(1)
+    if a.dtype != g.dtype or grad_b.dtype != a.dtype:
+        raise RuntimeError(f"segment_mm_grad_b: dtypes differ: {a.dtype}, {g.dtype}, {grad_b.dtype}")
+    if a.stride(1) != 1 or g.stride(1) != 1 or not grad_b.is_contiguous():
+        raise RuntimeError("segment_mm_grad_b: operands of unexpected layout")
+    chunk, max_chunks, nbytes = segment_mm_grad_b_workspace(a.dtype, n, plan.n_seg, d1, d2)
+    chunk_ptr, part_ptr = plan.chunks(chunk)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(
+            load_library().tsgu_segment_mm_grad_b(
+                vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, _p(plan.offsets), _p(chunk_ptr), _p(part_ptr), chunk,
+                max_chunks, _p(plan.perm), _p(a), max(a.stride(0), d1), _p(g), max(g.stride(0), d2), _p(grad_b), _p(ws), nbytes,
+                dev.index, _stream(dev),
+            ),
+            "tsgu_segment_mm_grad_b",
+        )
+    return grad_b
+
+
 def csr_sptrsm(ptr, idx, val, B, n: int, lower: bool, unit: bool, perm=None, wg_per_cu: int = 1):
     """X = M^{-1} B for the row-gather structure (ptr, idx, [perm], val) of a triangular M.  `wg_per_cu`: persistent workgroups per
     compute unit (1 … 8; speed only, see include/tsgu_hip.h)."""
@@ -870,7 +949,7 @@ def csr_sptrsm(ptr, idx, val, B, n: int, lower: bool, unit: bool, perm=None, wg_
     return X
 
 
-_PENDING = []            # (event, pinned int32 slot, what)
+_PENDING = []            # (event or None, pinned / host int32 slot, what, tsgu status)
 _PENDING_LOCK = threading.Lock()
 # Default: the error word of a solve is read back before X is handed out (one host sync per solve; a C3-sized solve takes
 # milliseconds).  TSGU_SPTRSM_CHECK=lazy defers the check (X is then UNVERIFIED until `poll_errors()` — exported by the
@@ -878,11 +957,22 @@ _PENDING_LOCK = threading.Lock()
 _SYNC_CHECK = os.environ.get("TSGU_SPTRSM_CHECK", "sync") != "lazy"
 
 
-def _defer_error_check(word: torch.Tensor, dev: torch.device, what: str = "tsgu_csr_sptrsm (dependency wait)") -> None:
+def _defer_error_check(word: torch.Tensor, dev: torch.device, what: str = "tsgu_csr_sptrsm (dependency wait)",
+                       status: int = -7) -> None:
+    """Report a non-zero int32 error `word` as tsgu `status`: at once by default, at the next `poll_errors()` when lazy.  A word
+    on the CPU (operands of the torch-op path) is already complete."""
+    if not word.is_cuda:
+        if _SYNC_CHECK:
+            if int(word.item()) != 0:
+                check(status, what)
+            return
+        with _PENDING_LOCK:
+            _PENDING.append((None, word.reshape(1).to(torch.int32), what, status))
+        return
     capturing = torch.cuda.is_current_stream_capturing()
     if _SYNC_CHECK and not capturing:
         if int(word.item()) != 0:
-            check(-7, what)
+            check(status, what)
         return
     if capturing:
         return      # (a graph replay cannot report through the host; the 4 s device-side bound still ends the wait)
@@ -892,7 +982,7 @@ def _defer_error_check(word: torch.Tensor, dev: torch.device, what: str = "tsgu_
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     with _PENDING_LOCK:
-        _PENDING.append((ev, host, what))
+        _PENDING.append((ev, host, what, status))
 
 
 def _poll_at_exit() -> None:
@@ -917,19 +1007,19 @@ def poll_errors(block: bool = False) -> None:
         items = list(_PENDING)
         _PENDING.clear()
     keep, failed = [], None
-    for ev, host, what in items:
-        if block:
+    for ev, host, what, status in items:
+        if block and ev is not None:
             ev.synchronize()
-        if ev.query():
+        if ev is None or ev.query():
             if int(host.item()) != 0 and failed is None:
-                failed = what
+                failed = (status, what)
         else:
-            keep.append((ev, host, what))
+            keep.append((ev, host, what, status))
     if keep:
         with _PENDING_LOCK:
             _PENDING[:0] = keep
     if failed is not None:
-        check(-7, failed)
+        check(*failed)
 
 
 def index_fingerprint(*tensors: torch.Tensor) -> torch.Tensor:

@@ -17,6 +17,9 @@ gathers · mul · sum  :186-205              :func:`sddmm`, in entry chunks: the
 column dots of the Krylov loops            :func:`coldot`
 ``_scatter_logsumexp``  sparse_logsumexp.py:10-73   :func:`segment_logsumexp` / :func:`segment_logsumexp_backward` on the
                                            segments of a cached pattern (every stored entry is one term)
+nested-tensor ``segment_mm`` / ``gather_mm``        :func:`segment_mm` / :func:`segment_mm_grad_b`: rows in plan order (a
+  indexed_matmul.py:95-105, :203-217       stable argsort of ``idx_b`` for gather_mm), one ``torch.matmul`` per segment,
+                                           scattered back
 =========================================  ====================================================================
 """
 
@@ -141,3 +144,30 @@ def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx) ->
         j = idx.reshape(-1).to(torch.int64)
         grad = grad + g_idx.to(acc)[j] * (v - lse_idx.to(acc)[j]).exp()
     return grad.to(val.dtype)
+
+
+def segment_mm(bounds, perm, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """out[perm[i]] = a[perm[i]] @ b[r] for the positions i in [bounds[r], bounds[r + 1]) (perm None: identity); rows outside
+    [bounds[0], bounds[-1]) are zeros.  One torch.matmul per segment; `b` may be a transposed view."""
+    _cpu_only(a, b, perm)
+    n, d2 = a.size(0), b.size(-1)
+    ap = a if perm is None else a.index_select(0, perm)
+    res = torch.zeros((n, d2), dtype=a.dtype)
+    for r in range(len(bounds) - 1):
+        lo, hi = bounds[r], bounds[r + 1]
+        if hi > lo:
+            res[lo:hi] = torch.matmul(ap[lo:hi], b[r])
+    return res if perm is None else torch.zeros_like(res).index_copy_(0, perm, res)
+
+
+def segment_mm_grad_b(bounds, perm, a: torch.Tensor, g: torch.Tensor, n_seg: int) -> torch.Tensor:
+    """grad_b[r] = a[perm[i]]ᵀ g[perm[i]] summed over the positions i of segment r (zeros for an empty segment)."""
+    _cpu_only(a, g, perm)
+    ap = a if perm is None else a.index_select(0, perm)
+    gp = g if perm is None else g.index_select(0, perm)
+    out = torch.zeros((n_seg, a.size(1), g.size(1)), dtype=a.dtype)
+    for r in range(n_seg):
+        lo, hi = bounds[r], bounds[r + 1]
+        if hi > lo:
+            out[r] = torch.matmul(ap[lo:hi].t(), gp[lo:hi])
+    return out
