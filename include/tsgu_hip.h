@@ -713,6 +713,60 @@ int tsgu_segment_mm_grad_b(int vtype, int itype, int64_t n, int64_t d1, int64_t 
                            const void* a, int64_t lda, const void* g, int64_t ldg, void* grad_b, void* workspace,
                            int64_t workspace_bytes, int device, void* stream);
 
+/*
+ * Density of the sparse multivariate normal (SparseMultivariateNormal / SparseMultivariateNormalNative: log_prob, entropy,
+ * variance) without densifying the factor.
+ * replaces: L.to_dense(), its diagonal().log().sum() and the (z**2).sum(-1) behind a dense solve_triangular
+ *                                           torchsparsegradutils/distributions/sparse_multivariate_normal.py:576-589 (log_prob),
+ *           L.to_dense() and (L_dense**2).sum(-1)                      sparse_multivariate_normal.py:531-545 (variance),
+ *           and the dense backward autograd takes through both.
+ *
+ * Value types fp32 and fp64 (fp32 sums in fp32, fp64 in fp64; bf16 is refused with TSGU_ERR_BAD_DTYPE).  Every sum over rows is
+ * two-stage in a fixed order: one workgroup per chunk of rows of a batch item leaves one partial per output, a second kernel adds
+ * an output's partials in order.  No float atomics, no host synchronisation: the same operands give the same bits, and every
+ * launch can be captured.  `partial` holds (number of outputs) * tsgu_mvn_reduce_blocks(rows_per_item) accumulator elements
+ * (4 bytes for fp32, 8 for fp64); `partial_elems` is its size in elements.  A batched operand is its block-diagonal 2-D pattern:
+ * n_rows = items * rows_per_item.
+ */
+int64_t tsgu_mvn_reduce_blocks(int64_t rows_per_item);
+/* Once per pattern: pos[i] = position in the owner's value array of the first entry of row i with col == i (through `perm`
+ * when the pattern carries one, NULL = identity), -1 when the row stores no diagonal entry.  pos has the index type. */
+int tsgu_csr_diag_positions(int itype, int64_t n_rows, int64_t nnz, const void* crow, const void* col, const void* perm,
+                            void* pos, int device, void* stream);
+/* out[item] = sum_i log(val[pos[i]]) over the item's rows; pos[i] < 0 counts as log 0 = -inf and a negative entry gives NaN, as
+ * the dense formula does.  pos == NULL: val is a dense vector of n_rows elements and out[item] = sum_i log(val[i]) (the
+ * log-determinant of the LDL^T forms: both share this reduction).  n_val = elements of val. */
+int tsgu_diag_logsum(int vtype, int itype, int64_t n_rows, int64_t rows_per_item, int64_t n_val, const void* pos,
+                     const void* val, void* out, void* partial, int64_t partial_elems, int device, void* stream);
+/* Its gradient in the value array (nnz elements): g[item] / val[pos[i]] at the diagonal positions.  fill != 0: every entry of
+ * every row is written, zero off the diagonal (the zero fill and the scatter are one pass over crow / perm; rows own disjoint
+ * entries).  fill == 0: the diagonal entries of `grad` are updated in place on top of the gradient that is already there (the
+ * solve's or the product's).  pos == NULL (dense vector, crow and perm unused): grad[i] = g[item] / val[i]. */
+int tsgu_diag_logsum_backward(int vtype, int itype, int64_t n_rows, int64_t rows_per_item, int64_t nnz, const void* crow,
+                              const void* perm, const void* pos, const void* val, const void* g, void* grad, int fill,
+                              int device, void* stream);
+/* The Mahalanobis term  out[item * k + c] = sum_i w_i^{+-1} (Y[i,c] + E[i,c])^2  over the item's rows.  Element (i, c) of Y at
+ * Y[i * ldy + c * y_col_stride] (the solve's row-major result and the products' transposed views are both read in place), E
+ * likewise with its own strides (NULL: absent; the implicit unit diagonal's share of L^T d + d).  w_mode: 0 no weight, 1 multiply
+ * by w[i], 2 divide by w[i] (w: n contiguous elements). */
+int tsgu_quadform(int vtype, int64_t n, int64_t k, const void* Y, int64_t ldy, int64_t y_col_stride, const void* E,
+                  int64_t lde, int64_t e_col_stride, const void* w, int w_mode, int64_t rows_per_item, void* out,
+                  void* partial, int64_t partial_elems, int device, void* stream);
+/* One pass: grad_Y[i,c] = 2 g[item * k + c] w_i^{+-1} (Y + E)[i,c] (at grad_Y[i * ldg + c * g_col_stride]; also the gradient of
+ * E) and, when grad_w is given, grad_w[i] = sum_c g[item * k + c] (Y + E)[i,c]^2 (multiply) or its negative over w_i^2 (divide). */
+int tsgu_quadform_backward(int vtype, int64_t n, int64_t k, const void* Y, int64_t ldy, int64_t y_col_stride, const void* E,
+                           int64_t lde, int64_t e_col_stride, const void* w, int w_mode, int64_t rows_per_item, const void* g,
+                           void* grad_Y, int64_t ldg, int64_t g_col_stride, void* grad_w, int device, void* stream);
+/* The variance of the covariance forms: out[i] = add[i] + sum over the entries k of row i of val[k]^2 * w[col[k]]  (w, add
+ * optional; w has n_w elements).  Eight lanes per row, summed in a fixed order. */
+int tsgu_csr_row_sumsq(int vtype, int itype, int64_t n_rows, int64_t nnz, int64_t n_w, const void* crow, const void* col,
+                       const void* perm, const void* val, const void* w, const void* add, void* out, int device,
+                       void* stream);
+/* grad_val[k] = 2 g[row(k)] val[k] w[col[k]] in the value array's own order (every stored entry is written once). */
+int tsgu_csr_row_sumsq_backward(int vtype, int itype, int64_t n_rows, int64_t nnz, int64_t n_w, const void* crow,
+                                const void* col, const void* perm, const void* val, const void* w, const void* g, void* grad_val,
+                                int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

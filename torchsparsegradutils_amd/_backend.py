@@ -142,6 +142,16 @@ SIGNATURES = {
     "tsgu_bicg_vector": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
     "tsgu_coldot_max_blocks": (_i64, [_i64, _i64]),
     "tsgu_coldot": (_int, [_int, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _int, _ptr]),
+    "tsgu_mvn_reduce_blocks": (_i64, [_i64]),
+    "tsgu_csr_diag_positions": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_diag_logsum": (_int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_diag_logsum_backward": (_int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_quadform": (_int, [_int, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _int, _i64, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_quadform_backward": (
+        _int, [_int, _i64, _i64, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _int, _i64, _ptr, _ptr, _i64, _i64, _ptr, _int, _ptr],
+    ),
+    "tsgu_csr_row_sumsq": (_int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_csr_row_sumsq_backward": (_int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
 }
 
 
@@ -1112,3 +1122,171 @@ def device_info(index: int = 0):
     ncu, wave = _int(0), _int(0)
     check(lib.tsgu_device_info(index, name, 128, ctypes.byref(ncu), ctypes.byref(wave)), "tsgu_device_info")
     return name.value.decode(), ncu.value, wave.value
+
+
+# ---- density reductions of the sparse multivariate normal (csrc/mvn.hip) ----------------------------------------------------------
+MVN_DTYPES = (torch.float32, torch.float64)      # (fp32 sums in fp32, fp64 in fp64; bf16 is not offered)
+
+
+def _mvn_partial(n_out: int, rows_per_item: int, dtype: torch.dtype, dev: torch.device):
+    nb = load_library().tsgu_mvn_reduce_blocks(rows_per_item)
+    return torch.empty(max(n_out * nb, 1), dtype=dtype, device=dev)
+
+
+def _mvn_dtype(*tensors) -> None:
+    for t in tensors:
+        if t is not None and t.dtype not in MVN_DTYPES:
+            raise TypeError(f"the density kernels take float32 and float64 operands, got {t.dtype}")
+    kinds = {t.dtype for t in tensors if t is not None}
+    if len(kinds) > 1:
+        raise RuntimeError(f"expected all operands to have the same dtype, got {sorted(str(k) for k in kinds)}")
+
+
+def csr_diag_positions(crow, col, perm, n_rows: int):
+    """pos[i] = position in the owner's value array of row i's diagonal entry (-1: none stored), for a 2-D row-gather pattern."""
+    dev = require_device(crow, col, perm)
+    crow, col = crow.contiguous(), col.contiguous()
+    perm = None if perm is None else perm.contiguous()
+    if col.dtype != crow.dtype or (perm is not None and perm.dtype != crow.dtype):
+        raise RuntimeError("index dtypes differ")
+    if crow.numel() != n_rows + 1:
+        raise RuntimeError(f"a pattern of {n_rows} rows needs a row pointer of {n_rows + 1} words, got {crow.numel()}")
+    pos = torch.empty(n_rows, dtype=crow.dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_csr_diag_positions(itype_of(crow), n_rows, col.numel(), _p(crow), _p(col), _p(perm), _p(pos),
+                                                     dev.index, _stream(dev)), "tsgu_csr_diag_positions")
+    return pos
+
+
+def diag_logsum(pos, val, n_rows: int, rows_per_item: int):
+    """(items,) tensor of Σ_i log(val[pos[i]]) per item (pos None: Σ_i log(val[i]) of a dense vector of n_rows elements)."""
+    _mvn_dtype(val)
+    dev = require_device(pos, val)
+    val = val.contiguous()
+    if rows_per_item <= 0 or n_rows % rows_per_item or (pos is not None and pos.numel() != n_rows) or (pos is None and val.numel() != n_rows):
+        raise RuntimeError("diag_logsum: operands of unexpected size")
+    items = n_rows // rows_per_item
+    out = torch.empty(items, dtype=val.dtype, device=dev)
+    partial = _mvn_partial(items, rows_per_item, val.dtype, dev)
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_diag_logsum(vtype_of(val), itype_of(pos) if pos is not None else TSGU_I64, n_rows, rows_per_item,
+                                              val.numel(), _p(pos), _p(val), _p(out), _p(partial), partial.numel(), dev.index,
+                                              _stream(dev)), "tsgu_diag_logsum")
+    return out
+
+
+def diag_logsum_backward(crow, perm, pos, val, g, n_rows: int, rows_per_item: int, grad=None):
+    """Gradient of `diag_logsum` in the value array: written into a new array (zero off the diagonal), or added in place to the
+    diagonal entries of `grad`."""
+    _mvn_dtype(val, g, grad)
+    dev = require_device(crow, perm, pos, val, g, grad)
+    val, g = val.contiguous(), g.contiguous()
+    if g.numel() * rows_per_item != n_rows or (pos is not None and pos.numel() != n_rows):
+        raise RuntimeError("diag_logsum_backward: operands of unexpected size")
+    fill = grad is None
+    if fill:
+        grad = torch.empty_like(val)
+    elif not grad.is_contiguous() or grad.numel() != val.numel():
+        raise RuntimeError("diag_logsum_backward: the gradient to update must be contiguous and of the values' size")
+    if pos is not None:
+        crow = crow.contiguous()
+        perm = None if perm is None else perm.contiguous()
+        if crow.numel() != n_rows + 1 or crow.dtype != pos.dtype or (perm is not None and perm.dtype != pos.dtype):
+            raise RuntimeError("diag_logsum_backward: index arrays of unexpected size or dtype")
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_diag_logsum_backward(
+            vtype_of(val), itype_of(pos) if pos is not None else TSGU_I64, n_rows, rows_per_item, val.numel(),
+            _p(crow) if pos is not None else None, _p(perm) if pos is not None else None, _p(pos), _p(val), _p(g), _p(grad),
+            int(fill), dev.index, _stream(dev)), "tsgu_diag_logsum_backward")
+    return grad
+
+
+def _quad_operands(Y, E, w, rows_per_item: int):
+    _mvn_dtype(Y, E, w)
+    dev = require_device(Y, E, w)
+    if Y.dim() != 2 or (E is not None and E.shape != Y.shape):
+        raise RuntimeError("quadform: Y (and E) must be 2-D arrays of one shape")
+    n, k = Y.shape
+    if rows_per_item <= 0 or n % rows_per_item:
+        raise RuntimeError("quadform: the rows are not a whole number of items")
+    if w is not None:
+        w = w.contiguous()
+        if w.numel() != n:
+            raise RuntimeError("quadform: one weight per row expected")
+    return dev, n, k, w
+
+
+def quadform(Y, E, w, w_mode: int, rows_per_item: int):
+    """(items, k) tensor of Σ_i w_i^{±1} (Y[i,c] + E[i,c])² per item; Y and E are read through their strides."""
+    dev, n, k, w = _quad_operands(Y, E, w, rows_per_item)
+    items = n // rows_per_item
+    out = torch.empty((items, k), dtype=Y.dtype, device=dev)
+    partial = _mvn_partial(items * k, rows_per_item, Y.dtype, dev)
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_quadform(
+            vtype_of(Y), n, k, _p(Y), Y.stride(0), Y.stride(1), _p(E), E.stride(0) if E is not None else 0,
+            E.stride(1) if E is not None else 0, _p(w), w_mode if w is not None else 0, rows_per_item, _p(out), _p(partial),
+            partial.numel(), dev.index, _stream(dev)), "tsgu_quadform")
+    return out
+
+
+def quadform_backward(Y, E, w, w_mode: int, rows_per_item: int, g, want_w: bool):
+    """(grad_Y in Y's layout, grad_w or None) of `quadform` for the upstream gradient g (items, k)."""
+    dev, n, k, w = _quad_operands(Y, E, w, rows_per_item)
+    _mvn_dtype(Y, g)
+    g = g.contiguous()
+    if g.numel() != (n // rows_per_item) * k or not g.is_cuda:
+        raise RuntimeError("quadform_backward: upstream gradient of unexpected size or device")
+    if k > 1 and Y.stride(0) == 1:
+        gY = torch.empty((k, n), dtype=Y.dtype, device=dev).t()      # a transposed view in, the same layout out
+    else:
+        gY = torch.empty((n, k), dtype=Y.dtype, device=dev)
+    gw = torch.empty(n, dtype=Y.dtype, device=dev) if (want_w and w is not None) else None
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_quadform_backward(
+            vtype_of(Y), n, k, _p(Y), Y.stride(0), Y.stride(1), _p(E), E.stride(0) if E is not None else 0,
+            E.stride(1) if E is not None else 0, _p(w), w_mode if w is not None else 0, rows_per_item, _p(g), _p(gY), gY.stride(0),
+            gY.stride(1), _p(gw), dev.index, _stream(dev)), "tsgu_quadform_backward")
+    return gY, gw
+
+
+def _sumsq_operands(crow, col, perm, val, w, n_rows: int):
+    _mvn_dtype(val, w)
+    dev = require_device(crow, col, perm, val, w)
+    crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
+    perm = None if perm is None else perm.contiguous()
+    w = None if w is None else w.contiguous()
+    if crow.numel() != n_rows + 1 or col.dtype != crow.dtype or (perm is not None and perm.dtype != crow.dtype) or col.numel() != val.numel():
+        raise RuntimeError("row_sumsq: index arrays of unexpected size or dtype")
+    return dev, crow, col, perm, val, w
+
+
+def csr_row_sumsq(crow, col, perm, val, w, add, n_rows: int):
+    """out[i] = add[i] + Σ_{k in row i} val[k]² w[col[k]]  (w, add optional)."""
+    dev, crow, col, perm, val, w = _sumsq_operands(crow, col, perm, val, w, n_rows)
+    _mvn_dtype(val, add)
+    add = None if add is None else add.contiguous()
+    if add is not None and (add.numel() != n_rows or not add.is_cuda):
+        raise RuntimeError("row_sumsq: one addend per row expected")
+    out = torch.empty(n_rows, dtype=val.dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_csr_row_sumsq(vtype_of(val), itype_of(crow), n_rows, val.numel(), w.numel() if w is not None else 0,
+                                                _p(crow), _p(col), _p(perm), _p(val), _p(w), _p(add), _p(out), dev.index,
+                                                _stream(dev)), "tsgu_csr_row_sumsq")
+    return out
+
+
+def csr_row_sumsq_backward(crow, col, perm, val, w, g, n_rows: int):
+    """grad_val[k] = 2 g[row(k)] val[k] w[col[k]] in the value array's order."""
+    dev, crow, col, perm, val, w = _sumsq_operands(crow, col, perm, val, w, n_rows)
+    _mvn_dtype(val, g)
+    g = g.contiguous()
+    if g.numel() != n_rows or not g.is_cuda:
+        raise RuntimeError("row_sumsq_backward: one upstream value per row expected")
+    grad = torch.empty_like(val) if n_rows else torch.zeros_like(val)
+    with torch.cuda.device(dev):
+        check(load_library().tsgu_csr_row_sumsq_backward(vtype_of(val), itype_of(crow), n_rows, val.numel(),
+                                                         w.numel() if w is not None else 0, _p(crow), _p(col), _p(perm), _p(val),
+                                                         _p(w), _p(g), _p(grad), dev.index, _stream(dev)),
+              "tsgu_csr_row_sumsq_backward")
+    return grad

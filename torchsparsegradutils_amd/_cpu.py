@@ -171,3 +171,102 @@ def segment_mm_grad_b(bounds, perm, a: torch.Tensor, g: torch.Tensor, n_seg: int
         if hi > lo:
             out[r] = torch.matmul(ap[lo:hi].t(), gp[lo:hi])
     return out
+
+
+# ---- density reductions of the sparse multivariate normal (the torch-op twins of csrc/mvn.hip) ------------------------------------
+def csr_diag_positions(crow: torch.Tensor, col: torch.Tensor, perm, n_rows: int) -> torch.Tensor:
+    """pos[i] = position in the owner's value array of the first entry of row i with col == i, -1 when the row stores none."""
+    _cpu_only(crow, col, perm)
+    counts = (crow[1:] - crow[:-1]).to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(n_rows), counts, output_size=col.numel())
+    hit = torch.nonzero(col.to(torch.int64) == rows).flatten()
+    big = col.numel()
+    first = torch.full((n_rows,), big, dtype=torch.int64).scatter_reduce(0, rows[hit], hit, "amin", include_self=True)
+    found = first < big
+    at = first.clamp(max=max(big - 1, 0))
+    own = at if perm is None else perm.to(torch.int64)[at] if big else at
+    return torch.where(found, own, torch.full_like(own, -1)).to(crow.dtype)
+
+
+def diag_logsum(pos, val: torch.Tensor, n_rows: int, rows_per_item: int) -> torch.Tensor:
+    """Σ_i log(val[pos[i]]) per item (pos None: of the dense vector val); a row without a stored diagonal is log 0 = -inf."""
+    _cpu_only(pos, val)
+    v = val.reshape(-1)
+    if pos is not None:
+        p = pos.to(torch.int64)
+        d = torch.where(p >= 0, v[p.clamp(min=0)] if v.numel() else torch.zeros(n_rows, dtype=v.dtype), torch.zeros((), dtype=v.dtype))
+    else:
+        d = v
+    return d.log().view(-1, rows_per_item).sum(dim=1)
+
+
+def diag_logsum_backward(pos, val: torch.Tensor, g: torch.Tensor, n_rows: int, rows_per_item: int, grad=None) -> torch.Tensor:
+    """g[item] / val[pos[i]] at the diagonal positions: into a zero array, or added in place to `grad`."""
+    _cpu_only(pos, val, g, grad)
+    v = val.reshape(-1)
+    ge = g.reshape(-1).repeat_interleave(rows_per_item)
+    if pos is None:
+        return ge / v
+    if grad is None:
+        grad = torch.zeros_like(v)
+    p = pos.to(torch.int64)
+    keep = p >= 0
+    grad.view(-1)[p[keep]] += ge[keep] / v[p[keep]]
+    return grad
+
+
+def _quad_weight(w, w_mode: int):
+    if w is None or w_mode == 0:
+        return None
+    return w.reshape(-1, 1) if w_mode == 1 else w.reshape(-1, 1).reciprocal()
+
+
+def quadform(Y: torch.Tensor, E, w, w_mode: int, rows_per_item: int) -> torch.Tensor:
+    """(items, k): Σ_i w_i^{±1} (Y[i,c] + E[i,c])² over the item's rows."""
+    _cpu_only(Y, E, w)
+    t = Y if E is None else Y + E
+    q = t * t
+    s = _quad_weight(w, w_mode)
+    if s is not None:
+        q = q * s
+    return q.view(-1, rows_per_item, Y.size(1)).sum(dim=1)
+
+
+def quadform_backward(Y: torch.Tensor, E, w, w_mode: int, rows_per_item: int, g: torch.Tensor, want_w: bool):
+    """(grad_Y, grad_w or None) of `quadform`."""
+    _cpu_only(Y, E, w, g)
+    t = Y if E is None else Y + E
+    ge = g.reshape(-1, 1, Y.size(1)).expand(-1, rows_per_item, -1).reshape(Y.shape)
+    s = _quad_weight(w, w_mode)
+    gY = 2 * ge * (t if s is None else s * t)
+    gw = None
+    if want_w and s is not None:
+        gw = (ge * t * t).sum(dim=1)
+        if w_mode == 2:
+            gw = -gw * (s * s).reshape(-1)
+    return gY, gw
+
+
+def csr_row_sumsq(plan: _pt.RowGather, values: torch.Tensor, w, add) -> torch.Tensor:
+    """out[i] = add[i] + Σ_{k in row i} val[k]² w[col[k]] on the 2-D plan."""
+    _cpu_only(values, w, add, plan.crow)
+    v = _values_in_plan_order(plan, values)
+    q = v * v
+    if w is not None:
+        q = q * w.reshape(-1)[plan.col.reshape(-1).to(torch.int64)]
+    out = torch.zeros(plan.n_rows, dtype=values.dtype).index_add_(0, plan.row_indices().reshape(-1).to(torch.int64), q)
+    return out if add is None else out + add.reshape(-1)
+
+
+def csr_row_sumsq_backward(plan: _pt.RowGather, values: torch.Tensor, w, g: torch.Tensor) -> torch.Tensor:
+    """grad_val[k] = 2 g[row(k)] val[k] w[col[k]] in the value array's order."""
+    _cpu_only(values, w, g, plan.crow)
+    v = _values_in_plan_order(plan, values)
+    q = 2 * g.reshape(-1)[plan.row_indices().reshape(-1).to(torch.int64)] * v
+    if w is not None:
+        q = q * w.reshape(-1)[plan.col.reshape(-1).to(torch.int64)]
+    if plan.perm is None:
+        return q
+    out = torch.empty_like(q)
+    out[plan.perm.reshape(-1).to(torch.int64)] = q
+    return out

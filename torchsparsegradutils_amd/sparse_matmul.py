@@ -368,3 +368,48 @@ class SparseMatMul(torch.autograd.Function):
                 gradB = gradB.view(ctx.B_shape)
 
         return gradA, gradB
+
+
+class _SparseTMatMul(torch.autograd.Function):
+    """``Aᵀ·D`` with sparsity-preserving gradients, without a materialised transpose of ``A``: the product the precision forms of
+    the sparse multivariate normal's density are built on (``y = Lᵀ d``).  Forward: K2, the gather product on the cached transposed
+    pattern; backward: ``grad_D = A·G`` (K1) and ``[∂A]_ij = ⟨D_i,:, G_j,:⟩`` at A's stored entries (K3 with the roles swapped),
+    returned with A's layout, index tensors and index dtype.  ``A``: COO or CSR ``(n, m)`` / ``(b, n, m)``; ``D``: dense
+    ``(n, p)`` / ``(b, n, p)``, a transposed view is read in place."""
+
+    @staticmethod
+    def forward(ctx, A, D):
+        if A.dim() != D.dim() or A.dim() not in (2, 3) or A.size(-2) != D.size(-2) or (A.dim() == 3 and A.size(0) != D.size(0)):
+            raise ValueError(f"incompatible operands for Aᵀ·D: A {tuple(A.shape)}, D {tuple(D.shape)}")
+        grad_flag = A.requires_grad or D.requires_grad
+        A, D = A.detach(), D.detach()
+        if A.device != D.device:
+            raise RuntimeError(f"A and D must be on the same device, got {A.device} and {D.device}")
+        if A.dtype != D.dtype:
+            raise RuntimeError(f"expected A and D to have the same dtype, got {A.dtype} and {D.dtype}")
+        op = _Operand(A)
+        Dk = D.reshape(-1, D.size(-1)) if op.flat_batch is not None else D
+        y = _ops.spmm_t(op.plan, op.values, Dk)
+        if op.flat_batch is not None:
+            y = y.view(D.size(0), A.size(-1), D.size(-1))
+        ctx.op, ctx.D_shape = op, D.shape
+        ctx.save_for_backward(op.values, Dk)
+        y.requires_grad_(grad_flag)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):  # type: ignore[override]
+        values, D = ctx.saved_tensors
+        op: _Operand = ctx.op
+        plan = op.plan
+        G = grad.reshape(-1, grad.size(-1)) if op.flat_batch is not None else grad
+        gradA = gradD = None
+        if ctx.needs_input_grad[0]:
+            if plan.perm is None:
+                gvals = _ops.sddmm(plan, G, D, swap_roles=True)
+            else:  # un-coalesced COO: one gradient entry per stored duplicate, in A's own order
+                gvals = _be.coo_sddmm(op.indices[0], op.indices[1], D, G)
+            gradA = op.rebuild(gvals)
+        if ctx.needs_input_grad[1]:
+            gradD = _ops.spmm(plan, values, G).view(ctx.D_shape)
+        return gradA, gradD
