@@ -504,6 +504,45 @@ int tsgu_csr_sptrsm(int vtype, int itype,
 int64_t tsgu_sptrsm_work_bytes(int64_t n, int64_t p);
 
 /*
+ * K4 on stencil factors: the same solve as a line sweep over a row-major lattice (csrc/sptrsm_lattice.hip).
+ * replaces: torch.triangular_solve(B, A, upper, transpose, unitriangular).solution
+ *           torchsparsegradutils/_compat.py:42-48  (from sparse_solve.py:181-183 and :202-204)
+ *
+ * For a matrix M (A, or Aᵀ walked through A's own arrays) whose rows are the points of a lattice,
+ * row = ((item·nx + x)·ny + y)·nz + z, and whose used entries (strictly below the diagonal for lower != 0, above otherwise) all
+ * point to a row of the same z-line or of a line (item, x, y) that comes EARLIER in the sweep (lexicographically smaller for a lower
+ * sweep, larger for an upper one) without wrapping around a lattice face.  One wave owns one z-line and solves its rows in z order;
+ * lines are handed out by one ticket counter in sweep order; dependencies between lines use the hand-off of tsgu_csr_sptrsm (X
+ * pre-filled with a NaN tag, one agent-scope store per element, bounded polls, the error word of `work`).  Every row sums its stored
+ * entries in the order and lane geometry of tsgu_csr_sptrsm: the solution is the same bits.  The index arrays are not read.
+ *
+ * The plan structure tsgu_trsm_lattice_plan lives on the host, its pointers are device pointers:
+ *   kind        0: M = A in stored order; 1: M = Aᵀ (values in the source rows of A's value array)
+ *   nlines, nz  z-lines (items·nx·ny) and rows per line; n = nlines·nz
+ *   ncls, width row classes (<= 255) and records per class (<= 32)
+ *   uniform_len > 0: row r of A starts at r·uniform_len in `val`; 0: at rstart[r]
+ *   front_lines lines a dependency front crosses (sizes the persistent grid when `workgroups` is 0; speed only)
+ *   tab         [ncls][width] records of two int32 in VISITING order (kind 0: stored order; kind 1: ascending source row):
+ *               word 0 = neighbour row − own row; word 1 = value position (kind 0: position in the own row; kind 1: position in
+ *               the source row) | 1<<8 used by a lower sweep | 1<<9 used by an upper sweep | 1<<10 diagonal | 1<<11 same line
+ *   lens        [ncls] uint8 stored entries per class;  rcls [n] uint8 class of every row;  rstart [n] int32 (uniform_len == 0)
+ * fp32 and fp64, p <= 64 (TSGU_ERR_TOO_LARGE beyond: the caller keeps tsgu_csr_sptrsm).  B(i, c) = B[i·ldb + c·b_col_stride], X row-major,
+ * X must not alias B.  `work`: tsgu_sptrsm_work_bytes() bytes.  `workgroups`: persistent 4-wave workgroups, 0 = chosen from
+ * front_lines (capped at 8 per compute unit and at the number of lines); the solution does not depend on it.
+ */
+typedef struct {
+    int32_t kind, nlines, nz, ncls, width, uniform_len, front_lines, reserved;
+    const void* tab;
+    const void* lens;
+    const void* rcls;
+    const void* rstart;
+} tsgu_trsm_lattice_plan;
+int tsgu_csr_sptrsm_lattice(int vtype, const tsgu_trsm_lattice_plan* plan, int64_t nnz, const void* val,
+                            int lower, int unit,
+                            const void* B, int64_t ldb, int64_t b_col_stride, void* X, int64_t ldx, int64_t p,
+                            void* work, int workgroups, int device, void* stream);
+
+/*
  * K5  fused CG vector updates (no preconditioner), all per-column scalars stay on the device.
  * replaces the ≈15-op chain  torchsparsegradutils/utils/linear_cg.py:64-95 (+ :27-47, :372-382)
  *

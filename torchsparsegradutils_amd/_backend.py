@@ -127,6 +127,7 @@ SIGNATURES = {
         [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _int, _int, _ptr],
     ),
     "tsgu_sptrsm_work_bytes": (_i64, [_i64, _i64]),
+    "tsgu_csr_sptrsm_lattice": (_int, [_int, _ptr, _i64, _ptr, _int, _int, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _int, _int, _ptr]),
     "tsgu_cg_fold_rows": (_i64, []),
     "tsgu_cg_alpha": (_int, [_int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _i64, _int, _ptr]),
     "tsgu_cg_update1": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
@@ -956,6 +957,37 @@ def csr_sptrsm(ptr, idx, val, B, n: int, lower: bool, unit: bool, perm=None, wg_
     # sync per solve); TSGU_SPTRSM_CHECK=lazy — and any solve inside a stream capture, where a host read is not allowed —
     # copies it asynchronously to pinned memory and examines it at the next solve / `poll_errors()`.
     _defer_error_check(work[512:516].view(torch.int32), dev)
+    return X
+
+
+def csr_sptrsm_lattice(tables, val, B, n: int, lower: bool, unit: bool, workgroups: int = 0):
+    """X = M^{-1} B by the line sweep (csrc/sptrsm_lattice.hip) for the lattice factor described by `tables`
+    (_lattice.trsm_tables of M's lattice plan for this sweep direction).  `workgroups`: persistent workgroups (0: the kernel's
+    rule; speed only).  Allocation, error word and capture behaviour as `csr_sptrsm`."""
+    lib = load_library()
+    dev = require_device(tables.tab, val, B)
+    if val.dtype != B.dtype:
+        raise RuntimeError(f"expected A and B to have the same dtype, got {val.dtype} and {B.dtype}")
+    if B.dim() != 2 or B.size(0) != n or tables.struct.nlines * tables.struct.nz != n or bool(tables.lower) != bool(lower):
+        raise RuntimeError(f"tsgu_csr_sptrsm_lattice: a {'lower' if lower else 'upper'} sweep over {n} rows needs a right-hand side of "
+                           f"{n} rows and the tables of that sweep, got {tuple(B.shape)} and tables of "
+                           f"{tables.struct.nlines * tables.struct.nz} rows ({'lower' if tables.lower else 'upper'})")
+    B, ldb, b_cs = strided2d(B)
+    p = B.size(-1)
+    val = val.contiguous()
+    X = torch.empty((n, p), dtype=B.dtype, device=dev)
+    if n == 0 or p == 0:
+        return X
+    work = torch.empty((lib.tsgu_sptrsm_work_bytes(n, p),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(
+            lib.tsgu_csr_sptrsm_lattice(
+                vtype_of(val), tables.struct_addr, val.numel(), _p(val), int(bool(lower)), int(bool(unit)), _p(B), ldb, b_cs,
+                _p(X), _ld(X), p, _p(work), int(workgroups), dev.index, _stream(dev),
+            ),
+            "tsgu_csr_sptrsm_lattice",
+        )
+    _defer_error_check(work[512:516].view(torch.int32), dev, "tsgu_csr_sptrsm_lattice (dependency wait)")
     return X
 
 

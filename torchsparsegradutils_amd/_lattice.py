@@ -56,12 +56,13 @@ class LatticePlan:
     live in the source rows of the owner's value array)."""
 
     __slots__ = ("kind", "nb", "nx", "ny", "nz", "ry", "rz", "ncls", "recw", "uniform_len", "codes", "ksrc", "lens",
-                 "lens_host", "rcls", "rstart", "n_rows", "nnz", "box", "_cfg", "_march")
+                 "lens_host", "rcls", "rstart", "n_rows", "nnz", "box", "_cfg", "_march", "_trsm")
 
     def __init__(self):
         self._cfg: Dict[tuple, "LatticeConfig"] = {}
         self.box = None              # (mask, periodic bits) when the pattern meets the plane-march condition (checked per row)
         self._march = False          # False: not derived yet; None: not a box stencil; else MarchTables
+        self._trsm = None            # None: not derived yet; else {lower: TrsmTables or None} (trsm_tables)
 
     def plan_bytes(self) -> int:
         total = 0
@@ -823,3 +824,154 @@ def linemarch_config_for(plan: LatticePlan, mode: int, vtype: int, p: int, lds_b
             cfg.struct_addr = ctypes.addressof(cfg.struct)
     mt._cfg[key] = cfg
     return cfg
+
+
+# ---- line-sweep triangular solve (csrc/sptrsm_lattice.hip): stencil factors ------------------------------------------------
+TRSM_USED_LOWER, TRSM_USED_UPPER, TRSM_DIAG, TRSM_INLINE = 1 << 8, 1 << 9, 1 << 10, 1 << 11
+
+
+class _TrsmLatticePlanStruct(ctypes.Structure):
+    """``tsgu_trsm_lattice_plan`` of include/tsgu_hip.h."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("kind", "nlines", "nz", "ncls", "width", "uniform_len", "front_lines", "reserved")] \
+        + [(k, ctypes.c_void_p) for k in ("tab", "lens", "rcls", "rstart")]
+
+
+class TrsmTables:
+    """What the line sweep needs of a lattice plan for one sweep direction: `tab_host` [classes][width][2] int32 records in VISITING
+    order (word 0: neighbour row − own row; word 1: value position | flags), the same table on the plan's device, the number of lines a
+    dependency front crosses and the ctypes image of ``tsgu_trsm_lattice_plan``."""
+
+    __slots__ = ("lower", "tab_host", "tab", "front_lines", "struct", "struct_addr")
+
+
+def _class_extents(plan: LatticePlan):
+    """(lo, hi): [3][classes] smallest / largest x, y, z among the rows of every class (host lists).  Whether a displacement wraps around
+    a lattice face depends on where the rows of its class sit, which the class table does not say: one pass over `rcls`."""
+    n, nx, ny, nz = plan.n_rows, plan.nx, plan.ny, plan.nz
+    dev = plan.rcls.device
+    r = torch.arange(n, device=dev, dtype=torch.int64)
+    coords = torch.stack((torch.div(r, ny * nz, rounding_mode="floor") % nx, torch.div(r, nz, rounding_mode="floor") % ny, r % nz))
+    idx = plan.rcls[:n].to(torch.int64).unsqueeze(0).expand(3, n)
+    lo = torch.full((3, plan.ncls), 1 << 30, dtype=torch.int64, device=dev).scatter_reduce_(1, idx, coords, "amin")
+    hi = torch.full((3, plan.ncls), -1, dtype=torch.int64, device=dev).scatter_reduce_(1, idx, coords, "amax")
+    both = torch.stack((lo, hi)).cpu().tolist()
+    return both[0], both[1]
+
+
+def _front_lines(nb: int, nx: int, ny: int, nz: int, sx: int, sy: int) -> int:
+    """Lines that are in flight together when line (x, y) starts sx·x + sy·y row steps after line (0, 0) and runs for nz steps."""
+    import numpy as np
+
+    start = np.sort((sx * np.arange(nx)[:, None] + sy * np.arange(ny)[None, :]).ravel())
+    return int(nb * (np.arange(1, start.size + 1) - np.searchsorted(start, start - nz, side="right")).max())
+
+
+def trsm_tables(plan: Optional[LatticePlan], lower: bool) -> Optional[TrsmTables]:
+    """TrsmTables of `plan` (the stored-order plan of M = A, or the kind-1 plan of M = Aᵀ) for a lower / upper sweep, or None when
+    the line sweep does not cover the pattern.  Host work on the class table, the geometry and the classes' extents; cached.
+
+    Eligible: the neighbour of every stored entry is the same number of rows away for all rows of its class (it wraps around a face
+    for all of them or for none), and every entry the sweep uses — strictly below the diagonal for `lower`, above otherwise — does not
+    wrap.  Its neighbour then lies on the own z-line at an earlier step, or on a line (item, x, y) that is drawn earlier (row-major
+    order is the lexicographic order of the coordinates).  Periodic triangular parts whose used entries wrap: None.  A transposed walk
+    that stores a source row twice in one row: None (its visiting order would be ambiguous)."""
+    if plan is None:
+        return None
+    if plan._trsm is None:
+        plan._trsm = _trsm_tables_both(plan)
+    return plan._trsm[bool(lower)]
+
+
+def _trsm_tables_both(plan: LatticePlan):
+    import numpy as np
+
+    none = {True: None, False: None}
+    nb, nx, ny, nz = plan.nb, plan.nx, plan.ny, plan.nz
+    if plan.ncls < 1 or plan.ncls > MAX_CLASSES or plan.recw > MAX_LEN or plan.n_rows != nb * nx * ny * nz or plan.n_rows >= 2**31:
+        return none
+    if plan.kind == 1 and plan.ksrc is None:
+        return none
+    # what the kernel keeps in LDS: the class records and lengths, and per wave at least one staged row of the widest operand it
+    # takes (64 fp64 columns) — a plan that does not fit 64 KiB is refused here, never by the launch
+    fixed = (plan.ncls * plan.recw * 8 + plan.ncls * 4 + 15) // 16 * 16
+    if fixed + 4 * (plan.recw * 8 + 64 * 8 + 16) > 64 * 1024:
+        return none
+    lo, hi = _class_extents(plan)
+    dims = (nx, ny, nz)
+    codes = plan.codes.tolist()
+    ksrc = plan.ksrc.tolist() if plan.kind == 1 else None
+    W = plan.recw
+    tab = np.zeros((plan.ncls, W, 2), dtype=np.int32)
+    ok = {True: True, False: True}
+    skew = {True: [None, None], False: [None, None]}        # per sweep: largest (dz | dy, dz) reach of the used entries with dx = 0 / dx != 0
+    for c in range(plan.ncls):
+        if lo[0][c] > hi[0][c]:
+            continue                                        # (a class without rows)
+        recs = []
+        for k, code in enumerate(codes[c]):
+            if code < 0:
+                continue
+            d = (code // 25 - 1, (code // 5) % 5 - 2, code % 5 - 2)
+            eff, wraps = [], False
+            for a in range(3):
+                da, na = d[a], dims[a]
+                if da == 0 or (lo[a][c] + da >= 0 and hi[a][c] + da < na):
+                    eff.append(da)
+                elif da < 0 and hi[a][c] + da < 0:
+                    eff.append(da + na)
+                    wraps = True
+                elif da > 0 and lo[a][c] + da >= na:
+                    eff.append(da - na)
+                    wraps = True
+                else:
+                    return none                             # wraps for some rows of the class only
+            off = (eff[0] * ny + eff[1]) * nz + eff[2]
+            if off == 0:
+                flags = TRSM_DIAG
+            else:
+                low = off < 0
+                flags = TRSM_USED_LOWER if low else TRSM_USED_UPPER
+                if wraps:
+                    ok[low] = False
+                elif eff[0] == 0 and eff[1] == 0:
+                    flags |= TRSM_INLINE                    # |dz| <= MAX_RADIUS = 2: the two solutions a wave keeps
+                else:
+                    sgn = -1 if low else 1                  # (mirrored for the upper sweep)
+                    sk = skew[low]
+                    if eff[0] == 0:
+                        sk[0] = max(sk[0] if sk[0] is not None else -9, sgn * -eff[2])
+                    else:
+                        cand = (sgn * -eff[1], sgn * -eff[2])
+                        sk[1] = cand if sk[1] is None else (max(sk[1][0], cand[0]), max(sk[1][1], cand[1]))
+            pos = ksrc[c][k] if plan.kind == 1 else k
+            if not 0 <= pos < 32:
+                return none
+            recs.append((off, pos | flags))
+        if plan.kind == 1:
+            recs.sort(key=lambda t: t[0])                   # the stored order of the transposed pattern: ascending source row
+            if any(a[0] == b[0] for a, b in zip(recs, recs[1:])):
+                return none
+        if len(recs) != int(plan.lens_host[c]) or len(recs) > W:
+            return none
+        for k, (off, info) in enumerate(recs):
+            tab[c, k, 0], tab[c, k, 1] = off, info
+    out = {}
+    dev = plan.rcls.device
+    tab_dev = None
+    for low in (True, False):
+        if not ok[low]:
+            out[low] = None
+            continue
+        sy = 0 if skew[low][0] is None else max(skew[low][0] + 1, 0)
+        sx = 0 if skew[low][1] is None else max(skew[low][1][1] + 1 + sy * max(skew[low][1][0], 0), 1)
+        if tab_dev is None:
+            tab_dev = torch.from_numpy(tab).to(dev)
+        t = TrsmTables()
+        t.lower, t.tab_host, t.tab = low, tab, tab_dev
+        t.front_lines = _front_lines(nb, nx, ny, nz, sx, sy)
+        t.struct = _TrsmLatticePlanStruct(plan.kind, nb * nx * ny, nz, plan.ncls, W, plan.uniform_len, t.front_lines, 0, tab_dev.data_ptr(),
+                                          plan.lens.data_ptr(), plan.rcls.data_ptr(), plan.rstart.data_ptr())
+        t.struct_addr = ctypes.addressof(t.struct)
+        out[low] = t
+    return out

@@ -103,13 +103,46 @@ def _solve(plan: _pt.RowGather, values, rhs, upper: bool, unit: bool, transpose:
         from . import _cpu
 
         return _cpu.sptrsm(plan, values, rhs, upper, unit, transpose)
-    pt = plan.transposed if transpose else plan      # transposed: rows of Aᵀ; the selected triangle flips side
-    lower = upper if transpose else not upper
+    lower = upper if transpose else not upper        # (transposed: rows of Aᵀ; the selected triangle flips side)
+    tables = _lattice_tables(plan, values, rhs, lower, transpose)
+    if tables is not None:
+        # a stencil factor on a lattice: the line sweep (csrc/sptrsm_lattice.hip) — the same bits, no wall-clock trial, and the
+        # transposed solve walks A's own arrays (no transposed pattern is built for it)
+        return _be.csr_sptrsm_lattice(tables, values, rhs, plan.n_rows, lower=lower, unit=unit, workgroups=TRSM_LATTICE_WORKGROUPS)
+    pt = plan.transposed if transpose else plan
 
     def run(wg_per_cu):
         return _be.csr_sptrsm(pt.crow, pt.col, values, rhs, pt.n_rows, lower=lower, unit=unit, perm=pt.perm, wg_per_cu=wg_per_cu)
 
     return run(_sweep_width(pt, lower, unit, rhs, run))
+
+
+# Line sweep for factors whose pattern is a stencil on a row-major lattice (what PairwiseEncoder emits; truncated 7- / 27-point
+# factors): one wave per z-line instead of one ticket and one pointer chase per row.  The solution is the same bits either way.
+# OFF by default (TSGU_ENABLE_TRSM_LATTICE=1 switches it on; the master switch TSGU_ENABLE_LATTICE=0 switches it off too): on the
+# flagship factor (64³ lattice, 8 columns) it measured 1.02-1.06x the sync-free sweep, not the 2x that was the bar for making it the
+# default; on lattices with long z-lines (15 x 17 x 1024) it is 4.9x faster (EXPERIMENTS.md §13).
+# TSGU_TRSM_LATTICE_CFG = persistent workgroups of the sweep (experiments; 0 = the kernel's rule).
+ENABLE_TRSM_LATTICE = os.environ.get("TSGU_ENABLE_TRSM_LATTICE", "0") == "1"
+TRSM_LATTICE_WORKGROUPS = int(os.environ.get("TSGU_TRSM_LATTICE_CFG", "0") or 0)
+TRSM_LATTICE_DTYPES = (torch.float32, torch.float64)
+TRSM_LATTICE_MAX_COLUMNS = 64
+
+
+def _lattice_tables(plan: _pt.RowGather, values, rhs, lower: bool, transpose: bool):
+    """Tables of the line sweep for this solve, or None: the switch, the operands the kernel takes (fp32 / fp64, one column tile),
+    then the pattern (`_ops._lattice_plan`: GPU operands, square, stored order, nnz >= PACK_MIN_NNZ, never first seen inside a stream
+    capture; `_lattice.trsm_tables`: the used entries reach back along the sweep without wrapping)."""
+    if not ENABLE_TRSM_LATTICE or values.dtype not in TRSM_LATTICE_DTYPES or rhs.dtype != values.dtype:
+        return None
+    if rhs.dim() != 2 or not 1 <= rhs.size(-1) <= TRSM_LATTICE_MAX_COLUMNS or values.numel() != plan.nnz:
+        return None
+    lp = _ops._lattice_plan(plan, transposed=transpose)
+    if lp is None:
+        return None
+    if lp._trsm is None and torch.cuda.is_current_stream_capturing():
+        return None          # (the tables are derived with one device reduction and a host read)
+    return _ops._lt.trsm_tables(lp, lower)
 
 
 # Persistent workgroups per CU of the sync-free sweep: a measured choice per (pattern, triangle, width), made at the pattern's
