@@ -178,6 +178,21 @@ def test_abi_library_exports_every_declared_symbol():
     assert lib.tsgu_sptrsm_work_bytes(10, 1) >= 516
 
 
+def test_launch_reports_the_symbol_it_called(monkeypatch):
+    """`_backend.launch` raises under the name of the symbol it called.  tsgu_coldot refuses p = 0 with TSGU_ERR_BAD_ARG before
+    it touches a device, so no kernel runs.  On a machine without a GPU torch cannot name a current device or stream: only there
+    the two queries `launch` makes are answered with device 0 / the null stream; the library call itself is the real one."""
+    from torchsparsegradutils_amd import _backend
+
+    if not torch.cuda.is_available():
+        monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+        monkeypatch.setattr(_backend, "_raw_stream", lambda dev: None)
+    with pytest.raises(RuntimeError) as e:
+        _backend.launch("tsgu_coldot", torch.device("cuda", 0), _backend.TSGU_F32, 8, 0, None, 0, None, 0, None, None)
+    status = _backend.load_library().tsgu_status_string(-2).decode()
+    assert "tsgu_coldot" in str(e.value) and status in str(e.value)
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "torchsparsegradutils_amd")
     for dirpath, _, files in os.walk(pkg):

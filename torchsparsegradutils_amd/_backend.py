@@ -238,27 +238,45 @@ def require_device(*tensors: torch.Tensor) -> torch.device:
     return dev
 
 
-def _stream(dev: torch.device) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
+def _raw_stream(dev: torch.device) -> int:
+    """Current HIP stream of `dev` as an integer handle (the accessor torch's own generated code uses: 0.1 us instead of 2)."""
+    return torch._C._cuda_getCurrentRawStream(dev.index)
+
+
+def launch(name: str, dev: torch.device, *args) -> None:
+    """The one way a kernel launch crosses the C ABI: calls the library's `name` with `args` — tensors as their data pointers,
+    None as NULL, everything else (sizes, flags, addresses that are already integers) as it is — followed by the device index
+    and the current stream of `dev`, and raises through `check` under the name that was called.  The stream is read here, at
+    call time: the same closure runs eagerly and under graph capture.  `dev` is made current only when it is not already
+    (`torch.cuda.device` costs ~8 us per launch; the library sets the device itself, the context puts torch's back)."""
+    fn = getattr(_lib or load_library(), name)
+    argv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    if torch.cuda.current_device() == dev.index:
+        rc = fn(*argv, dev.index, _raw_stream(dev))
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*argv, dev.index, _raw_stream(dev))
+    if rc:
+        check(rc, name)
 
 
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def is_transposed_view(t: torch.Tensor) -> bool:
+    """2-D operand with unit ROW stride (``x.t()`` of a contiguous matrix — what ``bvec.t()`` in the reference's sparse
+    multivariate normal hands over, distributions/sparse_multivariate_normal.py:96): consumed in place by K1 / K4."""
+    return t.dim() == 2 and t.size(0) > 1 and t.size(1) > 1 and t.stride(0) == 1 and t.stride(1) >= t.size(0)
+
+
 def strided2d(t: torch.Tensor):
     """(tensor, row stride, column stride) for a 2-D dense operand WITHOUT copying when it is row-major or a
-    transposed view (unit row stride — what ``bvec.t()`` in the reference's sparse multivariate normal hands over,
-    distributions/sparse_multivariate_normal.py:96); anything else is made contiguous."""
-    if t.dim() == 2 and t.size(0) > 1 and t.size(1) > 1 and t.stride(0) == 1 and t.stride(1) >= t.size(0):
+    transposed view; anything else is made contiguous."""
+    if is_transposed_view(t):
         return t, 1, t.stride(1)
     t = rowmajor(t)
     return t, _ld(t), 1
-
-
-def is_transposed_view(t: torch.Tensor) -> bool:
-    """2-D operand with unit ROW stride (``x.t()`` of a contiguous matrix): consumed in place by K1 / K4."""
-    return t.dim() == 2 and t.size(0) > 1 and t.size(1) > 1 and t.stride(0) == 1 and t.stride(1) >= t.size(0)
 
 
 def rowmajor(t: torch.Tensor) -> torch.Tensor:
@@ -321,21 +339,13 @@ def csr_spmm(crow, col, val, B, n_rows: int, n_cols: int, perm=None, out=None, d
         nblk = lib.tsgu_spmm_num_blocks(vt, n_rows, nnz, p, max_row_nnz)
         partial = torch.empty((batch * nblk, p), dtype=B.dtype, device=dev)
         dot_w = rowmajor(dot_w)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_spmm(
-                vt, itype_of(crow), n_rows, n_cols, nnz, _p(crow), _p(col), _p(val), _p(perm),
-                _p(B), ldb, b_cs, _bs(B), _p(out), ldc, c_cs, _bs(out), p, batch, max_row_nnz,
-                _p(dot_w), _ld(dot_w) if dot_w is not None else 0, _p(partial), dev.index, _stream(dev),
-            ),
-            "tsgu_csr_spmm",
-        )
+    launch("tsgu_csr_spmm", dev, vt, itype_of(crow), n_rows, n_cols, nnz, crow, col, val, perm, B, ldb, b_cs, _bs(B), out, ldc, c_cs,
+           _bs(out), p, batch, max_row_nnz, dot_w, _ld(dot_w) if dot_w is not None else 0, partial)
     return out if dot_w is None else (out, partial)
 
 
 def csr_sddmm(crow, col, G, B, n_rows: int, n_cols: int, alpha: float = 1.0, swap_roles: bool = False):
     """out[k] = alpha·<G[row k], B[col k]> (or roles swapped) for (batched) CSR patterns."""
-    lib = load_library()
     dev = require_device(crow, col, G, B)
     if G.dtype != B.dtype:
         raise RuntimeError(f"expected both dense operands to have the same dtype, got {G.dtype} and {B.dtype}")
@@ -346,21 +356,13 @@ def csr_sddmm(crow, col, G, B, n_rows: int, n_cols: int, alpha: float = 1.0, swa
     crow, col = crow.contiguous(), col.contiguous()
     nnz = col.size(-1)
     out = torch.empty(col.shape, dtype=G.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_sddmm(
-                vtype_of(G), itype_of(crow), n_rows, n_cols, nnz, _p(crow), _p(col),
-                _p(G), _ld(G), _bs(G), _p(B), _ld(B), _bs(B), _p(out), float(alpha), int(bool(swap_roles)),
-                p, batch, dev.index, _stream(dev),
-            ),
-            "tsgu_csr_sddmm",
-        )
+    launch("tsgu_csr_sddmm", dev, vtype_of(G), itype_of(crow), n_rows, n_cols, nnz, crow, col, G, _ld(G), _bs(G), B, _ld(B), _bs(B), out,
+           float(alpha), int(bool(swap_roles)), p, batch)
     return out
 
 
 def csr_mm_backward(tplan, val, G, B, n_rows: int, n_cols: int):
     """(gradA values in A's order, gradB) in one pass over the transposed plan `tplan` of A."""
-    lib = load_library()
     dev = require_device(tplan.crow, val, G, B)
     if not (val.dtype == G.dtype == B.dtype):
         raise RuntimeError("expected A, B and the upstream gradient to have the same dtype")
@@ -371,16 +373,8 @@ def csr_mm_backward(tplan, val, G, B, n_rows: int, n_cols: int):
     val = val.contiguous()
     gradA = torch.empty(val.shape, dtype=val.dtype, device=dev)
     gradB = torch.empty(B.shape, dtype=B.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_mm_backward(
-                vtype_of(val), itype_of(tplan.crow), n_rows, n_cols, tplan.col.size(-1),
-                _p(tplan.crow), _p(tplan.col), _p(tplan.perm), _p(val),
-                _p(G), _ld(G), _bs(G), _p(B), _ld(B), _bs(B), _p(gradA), _p(gradB), _ld(gradB), _bs(gradB),
-                p, batch, dev.index, _stream(dev),
-            ),
-            "tsgu_csr_mm_backward",
-        )
+    launch("tsgu_csr_mm_backward", dev, vtype_of(val), itype_of(tplan.crow), n_rows, n_cols, tplan.col.size(-1), tplan.crow, tplan.col,
+           tplan.perm, val, G, _ld(G), _bs(G), B, _ld(B), _bs(B), gradA, gradB, _ld(gradB), _bs(gradB), p, batch)
     return gradA, gradB
 
 
@@ -425,37 +419,23 @@ def rowpack_geometry(dtype: torch.dtype, p: int):
 
 def csr_spmm_rowpack(crow, val, rp, B, n_rows: int):
     """C = A·B through the row-pair union walk; `rp` is a _pattern.RowPackPlan of the walked pattern."""
-    lib = load_library()
     dev = require_device(crow, val, B)
     B = rowmajor(B)
     p = B.size(-1)
     out = torch.empty((n_rows, p), dtype=B.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_spmm_rowpack(
-                vtype_of(val), itype_of(crow), n_rows, B.size(0), rp.nnz, _p(crow), _plan_struct(rp), _p(val.contiguous()),
-                _p(B), _ld(B), _p(out), _ld(out), p, dev.index, _stream(dev),
-            ),
-            "tsgu_csr_spmm_rowpack",
-        )
+    launch("tsgu_csr_spmm_rowpack", dev, vtype_of(val), itype_of(crow), n_rows, B.size(0), rp.nnz, crow, _plan_struct(rp), val.contiguous(),
+           B, _ld(B), out, _ld(out), p)
     return out
 
 
 def csr_sddmm_rowpack(crow, rp, R, Cm, n_rows: int, alpha: float = 1.0):
     """out[k] = alpha·<R[row k], Cm[col k]> in stored order through the row-pair union walk (plan of a stored-order pattern)."""
-    lib = load_library()
     dev = require_device(crow, R, Cm)
     R, Cm = rowmajor(R), rowmajor(Cm)
     p = R.size(-1)
     out = torch.empty((rp.nnz,), dtype=R.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_sddmm_rowpack(
-                vtype_of(R), itype_of(crow), n_rows, Cm.size(0), rp.nnz, _p(crow), _plan_struct(rp), _p(R), _ld(R), _p(Cm),
-                _ld(Cm), _p(out), float(alpha), p, dev.index, _stream(dev),
-            ),
-            "tsgu_csr_sddmm_rowpack",
-        )
+    launch("tsgu_csr_sddmm_rowpack", dev, vtype_of(R), itype_of(crow), n_rows, Cm.size(0), rp.nnz, crow, _plan_struct(rp), R, _ld(R), Cm,
+           _ld(Cm), out, float(alpha), p)
     return out
 
 
@@ -485,47 +465,34 @@ def _tile_struct(tp):
 
 def csr_spmm_tile(tp, val, B):
     """C = A·B (a plan with value chunks `cpos` / `cslot`: Aᵀ·G through A's own values) by the row-block tile walk."""
-    lib = load_library()
     dev = require_device(val, B)
     B = rowmajor(B)
     p = B.size(-1)
     out = torch.empty((tp.n_rows, p), dtype=B.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.tsgu_csr_spmm_tile(vtype_of(val), _tile_struct(tp), _p(val.contiguous()), _p(B), _ld(B), _p(out), _ld(out), p, dev.index,
-                                     _stream(dev)), "tsgu_csr_spmm_tile")
+    launch("tsgu_csr_spmm_tile", dev, vtype_of(val), _tile_struct(tp), val.contiguous(), B, _ld(B), out, _ld(out), p)
     return out
 
 
 def csr_sddmm_tile(tp, R, Cm, alpha: float = 1.0):
     """out[k] = alpha·<R[row k], Cm[col k]> in stored order by the row-block tile walk (plan of a stored-order pattern)."""
-    lib = load_library()
     dev = require_device(R, Cm)
     R, Cm = rowmajor(R), rowmajor(Cm)
     p = R.size(-1)
     out = torch.empty((tp.nnz,), dtype=R.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.tsgu_csr_sddmm_tile(vtype_of(R), _tile_struct(tp), _p(R), _ld(R), _p(Cm), _ld(Cm), _p(out), float(alpha), p, dev.index,
-                                      _stream(dev)), "tsgu_csr_sddmm_tile")
+    launch("tsgu_csr_sddmm_tile", dev, vtype_of(R), _tile_struct(tp), R, _ld(R), Cm, _ld(Cm), out, float(alpha), p)
     return out
 
 
 def csr_mm_backward_rowpack(tcrow, rp, val, G, B, n_rows_t: int):
     """(gradA values in A's order, gradB) in one pass over the transposed pattern's RowPackPlan."""
-    lib = load_library()
     dev = require_device(tcrow, val, G, B)
     G, B = rowmajor(G), rowmajor(B)
     p = G.size(-1)
     val = val.contiguous()
     grad_a = torch.empty_like(val)
     grad_b = torch.empty((n_rows_t, p), dtype=G.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_mm_backward_rowpack(
-                vtype_of(val), itype_of(tcrow), n_rows_t, G.size(0), rp.nnz, _p(tcrow), _plan_struct(rp), _p(val), _p(G), _ld(G),
-                _p(B), _ld(B), _p(grad_a), _p(grad_b), _ld(grad_b), p, dev.index, _stream(dev),
-            ),
-            "tsgu_csr_mm_backward_rowpack",
-        )
+    launch("tsgu_csr_mm_backward_rowpack", dev, vtype_of(val), itype_of(tcrow), n_rows_t, G.size(0), rp.nnz, tcrow, _plan_struct(rp), val, G,
+           _ld(G), B, _ld(B), grad_a, grad_b, _ld(grad_b), p)
     return grad_a, grad_b
 
 
@@ -577,33 +544,23 @@ def lattice_rows(crow, col, dims, status, slot, thash=None, trep=None, remap=Non
     """Row analysis kernels of csrc/lattice_plan.hip: pass 1 (hash -> slot table) when `ctable` is None, pass 2 (class
     assignment + exact check) otherwise; the rows of the transposed pattern when `disp` is given.  `box_mask` / `periodic`
     (pass 2 of the stored-order walk): also the plane-march condition, status[4]."""
-    lib = _lib or load_library()
     dev = require_device(crow, col, status)
     nb, nx, ny, nz = dims
-    with _on_device(dev):
-        rc = lib.tsgu_lattice_rows(itype_of(crow), crow.numel() - 1, _p(crow), _p(col), nb, nx, ny, nz, _p(disp),
-                                   0 if disp is None else disp.numel(), _p(slot), _p(thash), _p(trep), _p(remap), _p(ctable), _p(lens),
-                                   _p(rcls), _p(status), int(box_mask), int(periodic), dev.index, _stream(dev))
-    check(rc, "tsgu_lattice_rows")
+    launch("tsgu_lattice_rows", dev, itype_of(crow), crow.numel() - 1, crow, col, nb, nx, ny, nz, disp, 0 if disp is None else disp.numel(),
+           slot, thash, trep, remap, ctable, lens, rcls, status, int(box_mask), int(periodic))
 
 
 def lattice_block_classes(rcls, n_rows, dims, ty, tz, nseg, mask):
-    lib = _lib or load_library()
     dev = require_device(rcls, mask)
     nb, nx, ny, nz = dims
-    with _on_device(dev):
-        rc = lib.tsgu_lattice_block_classes(n_rows, _p(rcls), nb, nx, ny, nz, ty, tz, nseg, _p(mask), dev.index, _stream(dev))
-    check(rc, "tsgu_lattice_block_classes")
+    launch("tsgu_lattice_block_classes", dev, n_rows, rcls, nb, nx, ny, nz, ty, tz, nseg, mask)
 
 
 def lattice_row_codes(crow, col, dims, rows, out, disp=None):
-    lib = _lib or load_library()
     dev = require_device(crow, col, rows, out)
     nb, nx, ny, nz = dims
-    with _on_device(dev):
-        rc = lib.tsgu_lattice_row_codes(itype_of(crow), crow.numel() - 1, _p(crow), _p(col), nb, nx, ny, nz, _p(disp),
-                                        0 if disp is None else disp.numel(), _p(rows), rows.numel(), _p(out), dev.index, _stream(dev))
-    check(rc, "tsgu_lattice_row_codes")
+    launch("tsgu_lattice_row_codes", dev, itype_of(crow), crow.numel() - 1, crow, col, nb, nx, ny, nz, disp, 0 if disp is None else disp.numel(),
+           rows, rows.numel(), out)
 
 
 def march_lds_bytes(mode: int, vtype: int, p: int, ty: int, tz: int, ry: int, rz: int, ncls: int, threads: int) -> int:
@@ -646,35 +603,12 @@ def _timed_end(tok, dev: torch.device) -> None:
     KERNEL_EVENTS.append((tok[0], tok[1][0], tok[1][1]))
 
 
-class _on_device:
-    """`with torch.cuda.device(dev)` only when `dev` is not already current (the context manager costs ~8 us per launch)."""
-
-    __slots__ = ("ctx",)
-
-    def __init__(self, dev: torch.device):
-        self.ctx = None if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-
-
-def _raw_stream(dev: torch.device) -> int:
-    """Current HIP stream of `dev` as an integer handle (the accessor torch's own generated code uses: 0.1 us instead of 2)."""
-    return torch._C._cuda_getCurrentRawStream(dev.index)
-
-
 def csr_spmm_lattice(lp, cfg, val, B, dot: bool = False, skip: int = 0, dot_w=None, out=None):
     """C = A·B (plan kind 0) or Aᵀ·B for the transposed plan (kind 1; `val` in A's own order) by the plane sweep / plane march.
     `dot` (plane sweep, fp32, stored order): also the per-workgroup partial sums of <C[row], B[row]> per column — returns
     (C, partial [workgroups][p]), the Krylov loops' fused dot epilogue; `skip` (with `dot`): address of a device int32 — the launch
     does nothing when it is non-zero (iterations queued past the end of a solve); `dot_w` (with `dot`): the partial sums are of
     <C[row], dot_w[row]> instead; `out` (with `dot`): a contiguous (n_rows, p) tensor that receives C."""
-    lib = _lib or load_library()
     dev = B.device
     if not B.is_cuda or val.device != dev:
         require_device(val, B)
@@ -694,47 +628,25 @@ def csr_spmm_lattice(lp, cfg, val, B, dot: bool = False, skip: int = 0, dot_w=No
             raise RuntimeError("csr_spmm_lattice: the dot epilogue exists for the fp32 / fp64 stored-order plane sweep only")
         nwg = lp.nb * cfg.nseg * -(-lp.ny // cfg.ty) * -(-lp.nz // cfg.tz)
         partial = torch.empty((nwg, p), dtype=B.dtype, device=dev)
-        with _on_device(dev):
-            rc = lib.tsgu_csr_spmm_lattice_dot(_VTYPE[val.dtype], cfg.struct_addr, n_rows, lp.nnz, val.data_ptr(), B.data_ptr(), _ld(B),
-                                               out.data_ptr(), p, p, partial.data_ptr(), nwg, skip or None,
-                                               None if dot_w is None else dot_w.data_ptr(), dev.index, _raw_stream(dev))
-        if rc:
-            check(rc, "tsgu_csr_spmm_lattice_dot")
+        launch("tsgu_csr_spmm_lattice_dot", dev, _VTYPE[val.dtype], cfg.struct_addr, n_rows, lp.nnz, val, B, _ld(B), out, p, p, partial, nwg,
+               skip or None, dot_w)
         return out, partial
     tok = _timed("lattice_spmm_t" if transposed else "lattice_spmm", dev) if KERNEL_EVENTS is not None else None
-    index = dev.index
-    ctx = None if torch.cuda.current_device() == index else torch.cuda.device(dev)      # (the context manager costs ~8 us: only when needed)
-    if ctx is not None:
-        ctx.__enter__()
-    try:
-        ldb = B.stride(0) if B.size(0) > 1 else max(p, 1)
-        stream = torch._C._cuda_getCurrentRawStream(index)
-        if march:
-            ct = cfg.col_tile          # operands wider than 64 columns: one launch per tile of 64 columns
-            vt, sa, nnz, vp, bp, op = _VTYPE[val.dtype], cfg.struct_addr, lp.nnz, val.data_ptr(), B.data_ptr(), out.data_ptr()
-            fn = lib.tsgu_csr_spmm_march
-            tr = int(transposed)
-            rc = fn(vt, sa, tr, n_rows, nnz, vp, bp, ldb, op, p, ct, index, stream)
-            for j in range(ct, p, ct):
-                if rc:
-                    break
-                rc = fn(vt, sa, tr, n_rows, nnz, vp, bp + j * 4, ldb, op + j * 4, p, ct, index, stream)
-        else:
-            rc = lib.tsgu_csr_spmm_lattice(_VTYPE[val.dtype], cfg.struct_addr, n_rows, lp.nnz, val.data_ptr(), B.data_ptr(), ldb,
-                                           out.data_ptr(), p, p, index, stream)
-    finally:
-        if ctx is not None:
-            ctx.__exit__(None, None, None)
+    ldb = B.stride(0) if B.size(0) > 1 else max(p, 1)
+    if march:
+        ct = cfg.col_tile          # operands wider than 64 columns: one launch per tile of 64 columns
+        vt, bp, op = _VTYPE[val.dtype], B.data_ptr(), out.data_ptr()
+        for j in range(0, p, ct):
+            launch("tsgu_csr_spmm_march", dev, vt, cfg.struct_addr, int(transposed), n_rows, lp.nnz, val, bp + j * 4, ldb, op + j * 4, p, ct)
+    else:
+        launch("tsgu_csr_spmm_lattice", dev, _VTYPE[val.dtype], cfg.struct_addr, n_rows, lp.nnz, val, B, ldb, out, p, p)
     if tok is not None:
         _timed_end(tok, dev)
-    if rc:
-        check(rc, "tsgu_csr_spmm_march" if march else "tsgu_csr_spmm_lattice")
     return out
 
 
 def csr_sddmm_lattice(lp, cfg, R, Cm, alpha: float = 1.0):
     """out[k] = alpha·<R[row k], Cm[col k]> in stored order by the plane sweep (plan kind 0)."""
-    lib = _lib or load_library()
     dev = R.device
     if not R.is_cuda or Cm.device != dev:
         require_device(R, Cm)
@@ -747,31 +659,18 @@ def csr_sddmm_lattice(lp, cfg, R, Cm, alpha: float = 1.0):
     n_rows = lp.n_rows
     out = torch.empty((lp.nnz,), dtype=R.dtype, device=dev)
     tok = _timed("lattice_sddmm", dev) if KERNEL_EVENTS is not None else None
-    index = dev.index
-    ctx = None if torch.cuda.current_device() == index else torch.cuda.device(dev)
-    if ctx is not None:
-        ctx.__enter__()
-    try:
-        ldr = R.stride(0) if R.size(0) > 1 else max(p, 1)
-        ldc = Cm.stride(0) if Cm.size(0) > 1 else max(p, 1)
-        stream = torch._C._cuda_getCurrentRawStream(index)
-        if getattr(cfg, "march", False):
-            ct = cfg.col_tile          # operands wider than 64 columns: the dots of the later column tiles are added to the first
-            for j in range(0, p, ct):
-                rc = lib.tsgu_csr_sddmm_march(_VTYPE[R.dtype], cfg.struct_addr, n_rows, lp.nnz, R.data_ptr() + j * 4, ldr,
-                                              Cm.data_ptr() + j * 4, ldc, out.data_ptr(), float(alpha), int(j > 0), ct, index, stream)
-                if rc:
-                    break
-        else:
-            rc = lib.tsgu_csr_sddmm_lattice(_VTYPE[R.dtype], cfg.struct_addr, n_rows, lp.nnz, R.data_ptr(), ldr, Cm.data_ptr(), ldc,
-                                            out.data_ptr(), float(alpha), p, index, stream)
-    finally:
-        if ctx is not None:
-            ctx.__exit__(None, None, None)
+    ldr = R.stride(0) if R.size(0) > 1 else max(p, 1)
+    ldc = Cm.stride(0) if Cm.size(0) > 1 else max(p, 1)
+    if getattr(cfg, "march", False):
+        ct = cfg.col_tile          # operands wider than 64 columns: the dots of the later column tiles are added to the first
+        vt, rp, cp = _VTYPE[R.dtype], R.data_ptr(), Cm.data_ptr()
+        for j in range(0, p, ct):
+            launch("tsgu_csr_sddmm_march", dev, vt, cfg.struct_addr, n_rows, lp.nnz, rp + j * 4, ldr, cp + j * 4, ldc, out, float(alpha),
+                   int(j > 0), ct)
+    else:
+        launch("tsgu_csr_sddmm_lattice", dev, _VTYPE[R.dtype], cfg.struct_addr, n_rows, lp.nnz, R, ldr, Cm, ldc, out, float(alpha), p)
     if tok is not None:
         _timed_end(tok, dev)
-    if rc:
-        check(rc, "tsgu_csr_sddmm_lattice")
     return out
 
 
@@ -785,7 +684,6 @@ def coo_sddmm(row, col, G, B, alpha: float = 1.0):
 
         out = _cpu.coo_sddmm(row, col, G, B)
         return out if alpha == 1.0 else out.mul_(alpha)
-    lib = load_library()
     dev = require_device(row, col, G, B)
     if G.dtype != B.dtype:
         raise RuntimeError(f"expected both dense operands to have the same dtype, got {G.dtype} and {B.dtype}")
@@ -793,14 +691,7 @@ def coo_sddmm(row, col, G, B, alpha: float = 1.0):
     row, col = row.contiguous(), col.contiguous()
     nnz = row.numel()
     out = torch.empty((nnz,), dtype=G.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_coo_sddmm(
-                vtype_of(G), itype_of(row), nnz, _p(row), _p(col), _p(G), _ld(G), _p(B), _ld(B), _p(out),
-                float(alpha), G.size(-1), dev.index, _stream(dev),
-            ),
-            "tsgu_coo_sddmm",
-        )
+    launch("tsgu_coo_sddmm", dev, vtype_of(G), itype_of(row), nnz, row, col, G, _ld(G), B, _ld(B), out, float(alpha), G.size(-1))
     return out
 
 
@@ -817,27 +708,18 @@ def segment_logsumexp(ptr, perm, val, out, n_groups: int, nnz: int, include_zero
     """out[group] = log Σ exp over the segments [ptr[g], ptr[g+1]) of val (through perm when given), plus the absent entries of
     each group when include_zeros; group g lands at out[(g // groups_per_item) * item_stride + g % groups_per_item] and the
     padding of every item is set to -inf.  `out` may be a view into a larger buffer (only its data pointer is used)."""
-    lib = load_library()
     dev = require_device(ptr, perm, val, out, workspace)
     if perm is not None and perm.dtype != ptr.dtype:
         raise RuntimeError(f"index dtypes differ: {ptr.dtype} and {perm.dtype}")
     if out.dtype != val.dtype:
         raise RuntimeError(f"output dtype {out.dtype} differs from the values' {val.dtype}")
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_segment_logsumexp(
-                vtype_of(val), itype_of(ptr), n_groups, nnz, _p(ptr), _p(perm), _p(val), int(bool(include_zeros)), axis_len,
-                _p(out), groups_per_item, item_stride, _p(workspace), workspace.numel() * workspace.element_size(),
-                dev.index, _stream(dev),
-            ),
-            "tsgu_segment_logsumexp",
-        )
+    launch("tsgu_segment_logsumexp", dev, vtype_of(val), itype_of(ptr), n_groups, nnz, ptr, perm, val, int(bool(include_zeros)), axis_len, out,
+           groups_per_item, item_stride, workspace, workspace.numel() * workspace.element_size())
 
 
 def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx, n_groups: int):
     """grad[k] = g_grp[grp(k)]·exp(val[k] − lse_grp[grp(k)]) + g_idx[idx[k]]·exp(val[k] − lse_idx[idx[k]]) in stored order
     (either direction may be None)."""
-    lib = load_library()
     dev = require_device(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx)
     itp = ptr if ptr is not None else idx
     if ptr is not None and idx is not None and ptr.dtype != idx.dtype:
@@ -846,14 +728,8 @@ def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx, n_
         if t is not None and (t.dtype != val.dtype or not t.is_contiguous()):
             raise RuntimeError("group vectors must be contiguous and of the values' dtype")
     grad = torch.empty_like(val)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_segment_logsumexp_backward(
-                vtype_of(val), itype_of(itp), val.numel(), _p(val), _p(ptr), n_groups, _p(g_grp), _p(lse_grp), _p(idx),
-                _p(g_idx), _p(lse_idx), _p(grad), dev.index, _stream(dev),
-            ),
-            "tsgu_segment_logsumexp_backward",
-        )
+    launch("tsgu_segment_logsumexp_backward", dev, vtype_of(val), itype_of(itp), val.numel(), val, ptr, n_groups, g_grp, lse_grp, idx, g_idx,
+           lse_idx, grad)
     return grad
 
 
@@ -889,15 +765,8 @@ def segment_mm(plan, a, b, out):
         raise RuntimeError(f"segment_mm: dtypes differ: {a.dtype}, {b.dtype}, {out.dtype}")
     if a.stride(1) != 1 or out.stride(1) != 1 or b.dim() != 3 or b.size(1) != d1 or b.size(2) != d2:
         raise RuntimeError("segment_mm: operands of unexpected layout")
-    with torch.cuda.device(dev):
-        check(
-            load_library().tsgu_segment_mm(
-                vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, _p(plan.offsets), _p(plan.tile_ptr), plan.max_tiles,
-                _p(plan.perm), _p(a), max(a.stride(0), d1), _p(b), b.stride(0), b.stride(1), b.stride(2), _p(out),
-                max(out.stride(0), d2), dev.index, _stream(dev),
-            ),
-            "tsgu_segment_mm",
-        )
+    launch("tsgu_segment_mm", dev, vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, plan.offsets, plan.tile_ptr, plan.max_tiles,
+           plan.perm, a, max(a.stride(0), d1), b, b.stride(0), b.stride(1), b.stride(2), out, max(out.stride(0), d2))
     return out
 
 
@@ -913,15 +782,8 @@ def segment_mm_grad_b(plan, a, g, grad_b):
     chunk, max_chunks, nbytes = segment_mm_grad_b_workspace(a.dtype, n, plan.n_seg, d1, d2)
     chunk_ptr, part_ptr = plan.chunks(chunk)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            load_library().tsgu_segment_mm_grad_b(
-                vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, _p(plan.offsets), _p(chunk_ptr), _p(part_ptr), chunk,
-                max_chunks, _p(plan.perm), _p(a), max(a.stride(0), d1), _p(g), max(g.stride(0), d2), _p(grad_b), _p(ws), nbytes,
-                dev.index, _stream(dev),
-            ),
-            "tsgu_segment_mm_grad_b",
-        )
+    launch("tsgu_segment_mm_grad_b", dev, vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, plan.offsets, chunk_ptr, part_ptr, chunk,
+           max_chunks, plan.perm, a, max(a.stride(0), d1), g, max(g.stride(0), d2), grad_b, ws, nbytes)
     return grad_b
 
 
@@ -944,14 +806,8 @@ def csr_sptrsm(ptr, idx, val, B, n: int, lower: bool, unit: bool, perm=None, wg_
     if n == 0 or p == 0:
         return X  # nothing to solve (the kernel would not even initialise its error word)
     work = torch.empty((lib.tsgu_sptrsm_work_bytes(n, p),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_sptrsm(
-                vtype_of(val), itype_of(ptr), n, idx.numel(), _p(ptr), _p(idx), _p(perm), _p(val),
-                int(bool(lower)), int(bool(unit)), _p(B), ldb, b_cs, _p(X), _ld(X), p, _p(work), int(wg_per_cu), dev.index, _stream(dev),
-            ),
-            "tsgu_csr_sptrsm",
-        )
+    launch("tsgu_csr_sptrsm", dev, vtype_of(val), itype_of(ptr), n, idx.numel(), ptr, idx, perm, val, int(bool(lower)), int(bool(unit)), B, ldb,
+           b_cs, X, _ld(X), p, work, int(wg_per_cu))
     # error word sits behind the 64 ticket counters (struct TrsmWork in csrc/sptrsm.hip).  It is only ever set by the
     # 4 s device-side wait bound (a dependency that never arrives).  Default: read back before X is handed out (one host
     # sync per solve); TSGU_SPTRSM_CHECK=lazy — and any solve inside a stream capture, where a host read is not allowed —
@@ -979,14 +835,8 @@ def csr_sptrsm_lattice(tables, val, B, n: int, lower: bool, unit: bool, workgrou
     if n == 0 or p == 0:
         return X
     work = torch.empty((lib.tsgu_sptrsm_work_bytes(n, p),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_csr_sptrsm_lattice(
-                vtype_of(val), tables.struct_addr, val.numel(), _p(val), int(bool(lower)), int(bool(unit)), _p(B), ldb, b_cs,
-                _p(X), _ld(X), p, _p(work), int(workgroups), dev.index, _stream(dev),
-            ),
-            "tsgu_csr_sptrsm_lattice",
-        )
+    launch("tsgu_csr_sptrsm_lattice", dev, vtype_of(val), tables.struct_addr, val.numel(), val, int(bool(lower)), int(bool(unit)), B, ldb, b_cs,
+           X, _ld(X), p, work, int(workgroups))
     _defer_error_check(work[512:516].view(torch.int32), dev, "tsgu_csr_sptrsm_lattice (dependency wait)")
     return X
 
@@ -1067,14 +917,10 @@ def poll_errors(block: bool = False) -> None:
 def index_fingerprint(*tensors: torch.Tensor) -> torch.Tensor:
     """[len(tensors)][2] int64 device tensor: the 128-bit content fingerprint of each (contiguous) index tensor; queued on the
     current stream, nothing is read back here."""
-    lib = load_library()
     dev = require_device(*tensors)
     out = torch.zeros((len(tensors), 2), dtype=torch.int64, device=dev)      # (one fill for all the words; the launches accumulate)
-    with torch.cuda.device(dev):
-        for i, t in enumerate(tensors):
-            t = t.contiguous()
-            check(lib.tsgu_index_fingerprint(itype_of(t), t.numel(), _p(t), out[i].data_ptr(), 1, dev.index, _stream(dev)),
-                  "tsgu_index_fingerprint")
+    for i, t in enumerate(tensors):
+        launch("tsgu_index_fingerprint", dev, itype_of(t), t.numel(), t.contiguous(), out[i], 1)
     return out
 
 
@@ -1083,24 +929,20 @@ def index_fingerprint_match(tensors, refs=None, copy: bool = False, hash: bool =
     device tensor {fingerprint word 0, word 1, non-zero iff the tensor differs from its `refs` entry}, `copies` fresh contiguous
     copies of the tensors (None unless `copy`).  `hash=False` (with `refs`, without `copy`): compare only — the fingerprint words stay 0
     (equal tensors have their reference's fingerprint).  Queued on the current stream, nothing is read back here."""
-    lib = load_library()
     dev = require_device(*tensors)
     out = torch.zeros((len(tensors), 3), dtype=torch.int64, device=dev)
     copies = [] if copy else None
-    with torch.cuda.device(dev):
-        for i, t in enumerate(tensors):
-            t = t.contiguous()
-            r = None
-            if refs is not None:
-                r = refs[i]
-                if r.dtype != t.dtype or r.numel() != t.numel() or r.device != t.device or not r.is_contiguous():
-                    raise ValueError("index_fingerprint_match: a reference tensor does not have the geometry of its index tensor")
-            c = torch.empty_like(t) if copy else None
-            check(lib.tsgu_index_fingerprint_match(itype_of(t), t.numel(), _p(t), _p(r) if r is not None else None,
-                                                   _p(c) if c is not None else None, out[i].data_ptr(), 1 | (0 if hash or r is None or copy else 2), dev.index, _stream(dev)),
-                  "tsgu_index_fingerprint_match")
-            if copy:
-                copies.append(c)
+    for i, t in enumerate(tensors):
+        t = t.contiguous()
+        r = None
+        if refs is not None:
+            r = refs[i]
+            if r.dtype != t.dtype or r.numel() != t.numel() or r.device != t.device or not r.is_contiguous():
+                raise ValueError("index_fingerprint_match: a reference tensor does not have the geometry of its index tensor")
+        c = torch.empty_like(t) if copy else None
+        launch("tsgu_index_fingerprint_match", dev, itype_of(t), t.numel(), t, r, c, out[i], 1 | (0 if hash or r is None or copy else 2))
+        if copy:
+            copies.append(c)
     return out, copies
 
 
@@ -1121,24 +963,17 @@ def coldot(X, Y):
         raise RuntimeError("tsgu_coldot: more than 256 right-hand sides are not supported by the fused path")
     partial = torch.empty((nb, p), dtype=X.dtype, device=dev)
     out = torch.empty((p,), dtype=X.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(
-            lib.tsgu_coldot(vtype_of(X), n, p, _p(X), _ld(X), _p(Y), _ld(Y), _p(partial), _p(out), dev.index,
-                            _stream(dev)),
-            "tsgu_coldot",
-        )
+    launch("tsgu_coldot", dev, vtype_of(X), n, p, X, _ld(X), Y, _ld(Y), partial, out)
     return out
 
 
 def device_copy(src: torch.Tensor, dst: torch.Tensor) -> None:
     """dst <- src by the library's own 16-bytes-per-lane streaming kernel (the measured HBM ceiling of bench.py)."""
-    lib = load_library()
     dev = require_device(src, dst)
     nbytes = src.numel() * src.element_size()
     if dst.numel() * dst.element_size() != nbytes or not (src.is_contiguous() and dst.is_contiguous()):
         raise RuntimeError("device_copy: contiguous tensors of equal byte size expected")
-    with torch.cuda.device(dev):
-        check(lib.tsgu_device_copy(_p(src), _p(dst), nbytes, dev.index, _stream(dev)), "tsgu_device_copy")
+    launch("tsgu_device_copy", dev, src, dst, nbytes)
 
 
 def device_cu_count(index: int = 0) -> int:
@@ -1184,9 +1019,7 @@ def csr_diag_positions(crow, col, perm, n_rows: int):
     if crow.numel() != n_rows + 1:
         raise RuntimeError(f"a pattern of {n_rows} rows needs a row pointer of {n_rows + 1} words, got {crow.numel()}")
     pos = torch.empty(n_rows, dtype=crow.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_csr_diag_positions(itype_of(crow), n_rows, col.numel(), _p(crow), _p(col), _p(perm), _p(pos),
-                                                     dev.index, _stream(dev)), "tsgu_csr_diag_positions")
+    launch("tsgu_csr_diag_positions", dev, itype_of(crow), n_rows, col.numel(), crow, col, perm, pos)
     return pos
 
 
@@ -1200,10 +1033,8 @@ def diag_logsum(pos, val, n_rows: int, rows_per_item: int):
     items = n_rows // rows_per_item
     out = torch.empty(items, dtype=val.dtype, device=dev)
     partial = _mvn_partial(items, rows_per_item, val.dtype, dev)
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_diag_logsum(vtype_of(val), itype_of(pos) if pos is not None else TSGU_I64, n_rows, rows_per_item,
-                                              val.numel(), _p(pos), _p(val), _p(out), _p(partial), partial.numel(), dev.index,
-                                              _stream(dev)), "tsgu_diag_logsum")
+    launch("tsgu_diag_logsum", dev, vtype_of(val), itype_of(pos) if pos is not None else TSGU_I64, n_rows, rows_per_item, val.numel(), pos, val,
+           out, partial, partial.numel())
     return out
 
 
@@ -1225,11 +1056,8 @@ def diag_logsum_backward(crow, perm, pos, val, g, n_rows: int, rows_per_item: in
         perm = None if perm is None else perm.contiguous()
         if crow.numel() != n_rows + 1 or crow.dtype != pos.dtype or (perm is not None and perm.dtype != pos.dtype):
             raise RuntimeError("diag_logsum_backward: index arrays of unexpected size or dtype")
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_diag_logsum_backward(
-            vtype_of(val), itype_of(pos) if pos is not None else TSGU_I64, n_rows, rows_per_item, val.numel(),
-            _p(crow) if pos is not None else None, _p(perm) if pos is not None else None, _p(pos), _p(val), _p(g), _p(grad),
-            int(fill), dev.index, _stream(dev)), "tsgu_diag_logsum_backward")
+    launch("tsgu_diag_logsum_backward", dev, vtype_of(val), itype_of(pos) if pos is not None else TSGU_I64, n_rows, rows_per_item, val.numel(),
+           crow if pos is not None else None, perm if pos is not None else None, pos, val, g, grad, int(fill))
     return grad
 
 
@@ -1254,11 +1082,8 @@ def quadform(Y, E, w, w_mode: int, rows_per_item: int):
     items = n // rows_per_item
     out = torch.empty((items, k), dtype=Y.dtype, device=dev)
     partial = _mvn_partial(items * k, rows_per_item, Y.dtype, dev)
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_quadform(
-            vtype_of(Y), n, k, _p(Y), Y.stride(0), Y.stride(1), _p(E), E.stride(0) if E is not None else 0,
-            E.stride(1) if E is not None else 0, _p(w), w_mode if w is not None else 0, rows_per_item, _p(out), _p(partial),
-            partial.numel(), dev.index, _stream(dev)), "tsgu_quadform")
+    launch("tsgu_quadform", dev, vtype_of(Y), n, k, Y, Y.stride(0), Y.stride(1), E, E.stride(0) if E is not None else 0,
+           E.stride(1) if E is not None else 0, w, w_mode if w is not None else 0, rows_per_item, out, partial, partial.numel())
     return out
 
 
@@ -1274,11 +1099,8 @@ def quadform_backward(Y, E, w, w_mode: int, rows_per_item: int, g, want_w: bool)
     else:
         gY = torch.empty((n, k), dtype=Y.dtype, device=dev)
     gw = torch.empty(n, dtype=Y.dtype, device=dev) if (want_w and w is not None) else None
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_quadform_backward(
-            vtype_of(Y), n, k, _p(Y), Y.stride(0), Y.stride(1), _p(E), E.stride(0) if E is not None else 0,
-            E.stride(1) if E is not None else 0, _p(w), w_mode if w is not None else 0, rows_per_item, _p(g), _p(gY), gY.stride(0),
-            gY.stride(1), _p(gw), dev.index, _stream(dev)), "tsgu_quadform_backward")
+    launch("tsgu_quadform_backward", dev, vtype_of(Y), n, k, Y, Y.stride(0), Y.stride(1), E, E.stride(0) if E is not None else 0,
+           E.stride(1) if E is not None else 0, w, w_mode if w is not None else 0, rows_per_item, g, gY, gY.stride(0), gY.stride(1), gw)
     return gY, gw
 
 
@@ -1301,10 +1123,8 @@ def csr_row_sumsq(crow, col, perm, val, w, add, n_rows: int):
     if add is not None and (add.numel() != n_rows or not add.is_cuda):
         raise RuntimeError("row_sumsq: one addend per row expected")
     out = torch.empty(n_rows, dtype=val.dtype, device=dev)
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_csr_row_sumsq(vtype_of(val), itype_of(crow), n_rows, val.numel(), w.numel() if w is not None else 0,
-                                                _p(crow), _p(col), _p(perm), _p(val), _p(w), _p(add), _p(out), dev.index,
-                                                _stream(dev)), "tsgu_csr_row_sumsq")
+    launch("tsgu_csr_row_sumsq", dev, vtype_of(val), itype_of(crow), n_rows, val.numel(), w.numel() if w is not None else 0, crow, col, perm, val,
+           w, add, out)
     return out
 
 
@@ -1316,9 +1136,6 @@ def csr_row_sumsq_backward(crow, col, perm, val, w, g, n_rows: int):
     if g.numel() != n_rows or not g.is_cuda:
         raise RuntimeError("row_sumsq_backward: one upstream value per row expected")
     grad = torch.empty_like(val) if n_rows else torch.zeros_like(val)
-    with torch.cuda.device(dev):
-        check(load_library().tsgu_csr_row_sumsq_backward(vtype_of(val), itype_of(crow), n_rows, val.numel(),
-                                                         w.numel() if w is not None else 0, _p(crow), _p(col), _p(perm), _p(val),
-                                                         _p(w), _p(g), _p(grad), dev.index, _stream(dev)),
-              "tsgu_csr_row_sumsq_backward")
+    launch("tsgu_csr_row_sumsq_backward", dev, vtype_of(val), itype_of(crow), n_rows, val.numel(), w.numel() if w is not None else 0, crow, col,
+           perm, val, w, g, grad)
     return grad

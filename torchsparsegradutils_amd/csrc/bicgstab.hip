@@ -323,27 +323,17 @@ int tsgu_bicg_scalar(int vtype, int phase, const void* partial, int64_t n_partia
     if (phase != kBicgBeta && !partial) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // one partial set with very many rows (the K1 epilogue writes one row per workgroup): fold it first
-    const bool do_fold = fold != nullptr && phase != kBicgOmega && phase != kBicgBeta && n_partial > 4 * kFoldRows;
-    const int64_t chunk = (n_partial + kFoldRows - 1) / kFoldRows;
-#define TSGU_BODY                                                                                                  \
-    {                                                                                                              \
-        const V* src = (const V*)partial;                                                                          \
-        int64_t rows = n_partial;                                                                                  \
-        if (do_fold) {                                                                                             \
-            hipLaunchKernelGGL((colsum_fold_kernel<V>), dim3(kFoldRows), dim3(kBlock), 0, s, src, n_partial, p,    \
-                               chunk, (V*)fold, phase == kBicgInit ? (const int*)nullptr : (const int*)flags);     \
-            if (const int rc = check_launch()) return rc;                                                          \
-            src = (const V*)fold;                                                                                  \
-            rows = kFoldRows;                                                                                      \
-        }                                                                                                          \
-        hipLaunchKernelGGL((bicg_scalar_kernel<V>), dim3(1), dim3(kBlock), 0, s, phase, src, rows, set_stride, p,  \
-                           (V*)scal, flags, (V)abstol, (V)reltol, matvec_max, nmv0);                               \
-        return check_launch();                                                                                     \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        const V* src;
+        int64_t rows;
+        // only a single partial set is folded (OMEGA reads three, BETA none); INIT runs whatever the stop word says
+        if (const int rc = fold_partials<V>(partial, n_partial, p, fold, phase != kBicgOmega && phase != kBicgBeta,
+                                            phase == kBicgInit ? (const int*)nullptr : (const int*)flags, s, src, rows))
+            return rc;
+        return launch(bicg_scalar_kernel<V>, 1, s, phase, src, rows, set_stride, p, (V*)scal, flags, (V)abstol, (V)reltol, matvec_max,
+                      nmv0);
+    });
 }
 
 // which: 0 = update_p(pv, r, v)   1 = update_s(s, r, v -> partial)   2 = dots3(t, s, r0 -> partial[3])
@@ -358,33 +348,28 @@ int tsgu_bicg_vector(int vtype, int which, int64_t n, int64_t p, void* a0, void*
     if (!(aligned16(a0) && aligned16(a1) && aligned16(a2) && aligned16(a3) && aligned16(a4))) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_GO(KERNEL, ...)                                                                                       \
-    do {                                                                                                           \
-        if (g.vec == 1) hipLaunchKernelGGL((KERNEL<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, __VA_ARGS__);     \
-    } while (0)
-#define TSGU_BODY                                                                                                  \
-    {                                                                                                              \
-        constexpr int wide = VT<V>::kWide;                                                                         \
-        VecGeom g;                                                                                                 \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                                \
-        if (which == 0)                                                                                            \
-            TSGU_GO(bicg_update_p_kernel, n, p, (V*)a0, (const V*)a1, (const V*)a2, (const V*)scal, flags, g.lpr, g.rpp); \
-        else if (which == 1)                                                                                       \
-            TSGU_GO(bicg_update_s_kernel, n, p, (V*)a0, (const V*)a1, (const V*)a2, (const V*)scal, flags, g.lpr, g.rpp, \
-                    (V*)partial);                                                                                  \
-        else if (which == 2)                                                                                       \
-            TSGU_GO(bicg_dots3_kernel, n, p, (const V*)a0, (const V*)a1, (const V*)a2, flags, g.lpr, g.rpp, (V*)partial, \
-                    set_stride);                                                                                   \
-        else                                                                                                       \
-            TSGU_GO(bicg_update_x_kernel, n, p, (V*)a0, (V*)a1, (const V*)a2, (const V*)a3, (const V*)a4, (const V*)scal, \
-                    flags, g.lpr, g.rpp, (V*)partial, (const V*)nullptr);                                          \
-        return check_launch();                                                                                     \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-#undef TSGU_GO
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (which == 0)
+            return launch_lanes<V>(n, p, bicg_update_p_kernel<V, 1>, bicg_update_p_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+                return launch(kern, g.blocks, s, n, p, (V*)a0, (const V*)a1, (const V*)a2, (const V*)scal, flags, g.lpr, g.rpp);
+            });
+        if (which == 1)
+            return launch_lanes<V>(n, p, bicg_update_s_kernel<V, 1>, bicg_update_s_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+                return launch(kern, g.blocks, s, n, p, (V*)a0, (const V*)a1, (const V*)a2, (const V*)scal, flags, g.lpr, g.rpp,
+                              (V*)partial);
+            });
+        if (which == 2)
+            return launch_lanes<V>(n, p, bicg_dots3_kernel<V, 1>, bicg_dots3_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+                return launch(kern, g.blocks, s, n, p, (const V*)a0, (const V*)a1, (const V*)a2, flags, g.lpr, g.rpp, (V*)partial,
+                              set_stride);
+            });
+        return launch_lanes<V>(n, p, bicg_update_x_kernel<V, 1>, bicg_update_x_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (V*)a0, (V*)a1, (const V*)a2, (const V*)a3, (const V*)a4, (const V*)scal, flags, g.lpr,
+                          g.rpp, (V*)partial, (const V*)nullptr);
+        });
+    });
 }
 
 // The x / r update of a preconditioned iteration: r = s - omega*t; x = (x + omega*z) + alpha*q with q = M p, z = M s
@@ -396,24 +381,14 @@ int tsgu_bicg_update_x_precond(int vtype, int64_t n, int64_t p, void* x, void* r
     if (!(aligned16(x) && aligned16(r) && aligned16(s_) && aligned16(t) && aligned16(q) && aligned16(z))) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_BODY                                                                                                  \
-    {                                                                                                              \
-        constexpr int wide = VT<V>::kWide;                                                                         \
-        VecGeom g;                                                                                                 \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                                \
-        if (g.vec == 1)                                                                                            \
-            hipLaunchKernelGGL((bicg_update_x_kernel<V, 1, true>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p, (V*)x, \
-                               (V*)r, (const V*)s_, (const V*)t, (const V*)q, (const V*)scal, flags, g.lpr, g.rpp,   \
-                               (V*)partial, (const V*)z);                                                          \
-        else                                                                                                       \
-            hipLaunchKernelGGL((bicg_update_x_kernel<V, wide, true>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p, \
-                               (V*)x, (V*)r, (const V*)s_, (const V*)t, (const V*)q, (const V*)scal, flags, g.lpr,   \
-                               g.rpp, (V*)partial, (const V*)z);                                                   \
-        return check_launch();                                                                                     \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        return launch_lanes<V>(n, p, bicg_update_x_kernel<V, 1, true>, bicg_update_x_kernel<V, wide, true>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (V*)x, (V*)r, (const V*)s_, (const V*)t, (const V*)q, (const V*)scal, flags, g.lpr, g.rpp,
+                          (V*)partial, (const V*)z);
+        });
+    });
 }
 
 }  // extern "C"

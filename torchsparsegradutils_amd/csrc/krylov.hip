@@ -488,27 +488,17 @@ int tsgu_coldot(int vtype, int64_t n, int64_t p, const void* X, int64_t ldx, con
     if (n < 0 || p <= 0 || !X || !Y || !partial || !out || ldx < p || ldy < p) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_COLDOT_BODY                                                                                          \
-    {                                                                                                             \
-        constexpr int wide = VT<V>::kWide;                                                                        \
-        VecGeom g;                                                                                                \
-        const bool can = aligned16(X) && aligned16(Y) && ldx % wide == 0 && ldy % wide == 0 && p % wide == 0;    \
-        if (!vec_geom(wide, can, n, p, g)) return TSGU_ERR_TOO_LARGE;                                             \
-        if (g.blocks == 0) g.blocks = 1;                                                                          \
-        if (g.vec == 1)                                                                                           \
-            hipLaunchKernelGGL((coldot_partial_kernel<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p, \
-                               (const V*)X, ldx, (const V*)Y, ldy, g.lpr, g.rpp, (V*)partial);                   \
-        else                                                                                                      \
-            hipLaunchKernelGGL((coldot_partial_kernel<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, \
-                               p, (const V*)X, ldx, (const V*)Y, ldy, g.lpr, g.rpp, (V*)partial);                \
-        if (const int rc = check_launch()) return rc;                                                             \
-        hipLaunchKernelGGL((colsum_finalize_kernel<V>), dim3((unsigned)((p + 63) / 64)), dim3(kBlock), 0, s,      \
-                           (const V*)partial, g.blocks, p, (V*)out);                                              \
-        return check_launch();                                                                                    \
-    }
-    TSGU_VSWITCH(vtype, TSGU_COLDOT_BODY, TSGU_COLDOT_BODY);
-#undef TSGU_COLDOT_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        // (strided operands: wide lanes also need leading dimensions that keep every row 16-byte aligned)
+        const bool aligned = aligned16(X) && aligned16(Y) && ldx % wide == 0 && ldy % wide == 0;
+        return launch_lanes<V>(n, p, coldot_partial_kernel<V, 1>, coldot_partial_kernel<V, wide>, [&](auto kern, const VecGeom& g) -> int {
+            const int64_t blocks = g.blocks == 0 ? 1 : g.blocks;
+            if (const int rc = launch(kern, blocks, s, n, p, (const V*)X, ldx, (const V*)Y, ldy, g.lpr, g.rpp, (V*)partial)) return rc;
+            return launch(colsum_finalize_kernel<V>, (p + 63) / 64, s, (const V*)partial, blocks, p, (V*)out);
+        }, aligned);
+    });
 }
 
 int tsgu_cg_alpha(int vtype, const void* pap_partial, int64_t n_partial, void* fold, void* scal, int* flags,
@@ -516,27 +506,13 @@ int tsgu_cg_alpha(int vtype, const void* pap_partial, int64_t n_partial, void* f
     if (!pap_partial || !scal || !flags || p <= 0 || n_partial < 0) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // many partial rows (one per K1 workgroup): fold them to kFoldRows rows first (needs `fold`)
-    const bool do_fold = fold != nullptr && n_partial > 4 * kFoldRows;
-    const int64_t chunk = (n_partial + kFoldRows - 1) / kFoldRows;
-#define TSGU_BODY                                                                                              \
-    {                                                                                                          \
-        const V* src = (const V*)pap_partial;                                                                  \
-        int64_t rows = n_partial;                                                                              \
-        if (do_fold) {                                                                                         \
-            hipLaunchKernelGGL((colsum_fold_kernel<V>), dim3(kFoldRows), dim3(kBlock), 0, s, src, n_partial, p, \
-                               chunk, (V*)fold, (const int*)flags);                                            \
-            if (const int rc = check_launch()) return rc;                                                      \
-            src = (const V*)fold;                                                                              \
-            rows = kFoldRows;                                                                                  \
-        }                                                                                                      \
-        hipLaunchKernelGGL((cg_alpha_kernel<V>), dim3((unsigned)((p + 63) / 64)), dim3(kBlock), 0, s, src,      \
-                           rows, p, (V*)scal, (const int*)flags, (V)eps);                                      \
-        return check_launch();                                                                                 \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        const V* src;
+        int64_t rows;
+        if (const int rc = fold_partials<V>(pap_partial, n_partial, p, fold, true, flags, s, src, rows)) return rc;
+        return launch(cg_alpha_kernel<V>, (p + 63) / 64, s, src, rows, p, (V*)scal, (const int*)flags, (V)eps);
+    });
 }
 
 int tsgu_cg_update1(int vtype, int64_t n, int64_t p, void* r, const void* Ap, void* x, const void* pvec,
@@ -545,25 +521,15 @@ int tsgu_cg_update1(int vtype, int64_t n, int64_t p, void* r, const void* Ap, vo
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // rr_partial has tsgu_cg_num_blocks(vtype, n, p) rows; that count assumes aligned operands.
-#define TSGU_BODY                                                                                               \
-    {                                                                                                           \
-        VecGeom g;                                                                                              \
-        constexpr int wide = VT<V>::kWide;                                                                      \
-        if (!(aligned16(r) && aligned16(Ap) && aligned16(x) && aligned16(pvec))) return TSGU_ERR_BAD_ARG;      \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                             \
-        if (g.vec == 1)                                                                                         \
-            hipLaunchKernelGGL((cg_update1_kernel<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p,   \
-                               (V*)r, (const V*)Ap, (V*)x, (const V*)pvec, (const V*)scal, flags, g.lpr, g.rpp, \
-                               (V*)rr_partial);                                                                 \
-        else                                                                                                    \
-            hipLaunchKernelGGL((cg_update1_kernel<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n,   \
-                               p, (V*)r, (const V*)Ap, (V*)x, (const V*)pvec, (const V*)scal, flags, g.lpr,     \
-                               g.rpp, (V*)rr_partial);                                                          \
-        return check_launch();                                                                                  \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (!(aligned16(r) && aligned16(Ap) && aligned16(x) && aligned16(pvec))) return TSGU_ERR_BAD_ARG;
+        return launch_lanes<V>(n, p, cg_update1_kernel<V, 1>, cg_update1_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (V*)r, (const V*)Ap, (V*)x, (const V*)pvec, (const V*)scal, flags, g.lpr, g.rpp,
+                          (V*)rr_partial);
+        });
+    });
 }
 
 int tsgu_cg_update1_alpha(int vtype, int64_t n, int64_t p, void* r, const void* Ap, void* x, const void* pvec, const void* pap_partial,
@@ -573,25 +539,15 @@ int tsgu_cg_update1_alpha(int vtype, int64_t n, int64_t p, void* r, const void* 
     if (n_partial > 1024) return TSGU_ERR_TOO_LARGE;      // (every workgroup reads all partial rows: use tsgu_cg_alpha + tsgu_cg_update1)
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_BODY                                                                                                     \
-    {                                                                                                                 \
-        VecGeom g;                                                                                                    \
-        constexpr int wide = VT<V>::kWide;                                                                            \
-        if (!(aligned16(r) && aligned16(Ap) && aligned16(x) && aligned16(pvec))) return TSGU_ERR_BAD_ARG;            \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                                   \
-        if (g.vec == 1)                                                                                               \
-            hipLaunchKernelGGL((cg_update1_alpha_kernel<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p,   \
-                               (V*)r, (const V*)Ap, (V*)x, (const V*)pvec, (const V*)pap_partial, n_partial,         \
-                               (V*)scal, flags, (V)eps, g.lpr, g.rpp, (V*)rr_partial);                               \
-        else                                                                                                          \
-            hipLaunchKernelGGL((cg_update1_alpha_kernel<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n,   \
-                               p, (V*)r, (const V*)Ap, (V*)x, (const V*)pvec, (const V*)pap_partial, n_partial,      \
-                               (V*)scal, flags, (V)eps, g.lpr, g.rpp, (V*)rr_partial);                               \
-        return check_launch();                                                                                        \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (!(aligned16(r) && aligned16(Ap) && aligned16(x) && aligned16(pvec))) return TSGU_ERR_BAD_ARG;
+        return launch_lanes<V>(n, p, cg_update1_alpha_kernel<V, 1>, cg_update1_alpha_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (V*)r, (const V*)Ap, (V*)x, (const V*)pvec, (const V*)pap_partial, n_partial,
+                          (V*)scal, flags, (V)eps, g.lpr, g.rpp, (V*)rr_partial);
+        });
+    });
 }
 
 int tsgu_cg_beta(int vtype, const void* rr_partial, int64_t n_partial, void* scal, int* flags, double eps,
@@ -607,16 +563,11 @@ int tsgu_cg_beta_precond(int vtype, const void* rr_partial, int64_t n_partial, c
     if (!rr_partial || !scal || !flags || p <= 0 || n_partial < 0 || n_rz < 0) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_BODY                                                                                             \
-    {                                                                                                         \
-        hipLaunchKernelGGL((cg_beta_kernel<V>), dim3(1), dim3(kBlock), 0, s, (const V*)rr_partial, n_partial, \
-                           p, (V*)scal, flags, (V)eps, (V)stop_updating_after, (V)tolerance, iter_index,      \
-                           min_iter_index, (const V*)rz_partial, n_rz);                                       \
-        return check_launch();                                                                                \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) {
+        using V = decltype(tag);
+        return launch(cg_beta_kernel<V>, 1, s, (const V*)rr_partial, n_partial, p, (V*)scal, flags, (V)eps, (V)stop_updating_after,
+                      (V)tolerance, iter_index, min_iter_index, (const V*)rz_partial, n_rz);
+    });
 }
 
 int tsgu_cg_update2(int vtype, int64_t n, int64_t p, const void* r, void* pvec, const void* scal,
@@ -624,23 +575,14 @@ int tsgu_cg_update2(int vtype, int64_t n, int64_t p, const void* r, void* pvec, 
     if (n <= 0 || p <= 0 || !r || !pvec || !scal || !flags) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_BODY                                                                                             \
-    {                                                                                                         \
-        constexpr int wide = VT<V>::kWide;                                                                    \
-        VecGeom g;                                                                                            \
-        if (!(aligned16(r) && aligned16(pvec))) return TSGU_ERR_BAD_ARG;                                      \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                           \
-        if (g.vec == 1)                                                                                       \
-            hipLaunchKernelGGL((cg_update2_kernel<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p, \
-                               (const V*)r, (V*)pvec, (const V*)scal, flags, g.lpr, g.rpp);                   \
-        else                                                                                                  \
-            hipLaunchKernelGGL((cg_update2_kernel<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, \
-                               p, (const V*)r, (V*)pvec, (const V*)scal, flags, g.lpr, g.rpp);                \
-        return check_launch();                                                                                \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (!(aligned16(r) && aligned16(pvec))) return TSGU_ERR_BAD_ARG;
+        return launch_lanes<V>(n, p, cg_update2_kernel<V, 1>, cg_update2_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (const V*)r, (V*)pvec, (const V*)scal, flags, g.lpr, g.rpp);
+        });
+    });
 }
 
 // ---- the two-launch form (see cg_residual_alpha_kernel) ----
@@ -661,28 +603,20 @@ int tsgu_cg2_residual(int vtype, int64_t n, int64_t p, void* r, const void* Ap, 
     if (n_partial > 1024) return TSGU_ERR_TOO_LARGE;      // (every workgroup reads all partial rows)
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_BODY                                                                                                          \
-    {                                                                                                                      \
-        VecGeom g;                                                                                                         \
-        constexpr int wide = VT<V>::kWide;                                                                                 \
-        if (!(aligned16(r) && aligned16(Ap))) return TSGU_ERR_BAD_ARG;                                                     \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                                        \
-        const int groups = cg2_groups(g.blocks);                                                                           \
-        const int64_t per = (int64_t)g.rpp * kPasses * groups;                                                             \
-        const unsigned blocks = (unsigned)((n + per - 1) / per);                                                           \
-        auto go = [&](auto kern) {                                                                                         \
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, s, n, p, (V*)r, (const V*)Ap, (const V*)pap_partial,   \
-                               n_partial, (V*)scal2, flags2, parity, (V)eps, g.lpr, g.rpp, groups, (V*)rr_partial);       \
-        };                                                                                                                 \
-        if (g.vec == 1) go(cg_residual_alpha_kernel<V, 1, 0>);                                                             \
-        else if (groups == 1) go(cg_residual_alpha_kernel<V, wide, 1>);                                                    \
-        else if (groups == 2) go(cg_residual_alpha_kernel<V, wide, 2>);                                                    \
-        else go(cg_residual_alpha_kernel<V, wide, 0>);                                                                     \
-        return check_launch();                                                                                             \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (!(aligned16(r) && aligned16(Ap))) return TSGU_ERR_BAD_ARG;
+        return launch_lanes<V>(n, p, cg_residual_alpha_kernel<V, 1, 0>, cg_residual_alpha_kernel<V, wide, 0>, [&](auto kern, const VecGeom& g) {
+            // a grid of its own: `groups` groups of row passes per workgroup; one or two of them (wide lanes) are unrolled instances
+            const int groups = cg2_groups(g.blocks);
+            const int64_t per = (int64_t)g.rpp * kPasses * groups;
+            if (g.vec != 1 && groups == 1) kern = cg_residual_alpha_kernel<V, wide, 1>;
+            else if (g.vec != 1 && groups == 2) kern = cg_residual_alpha_kernel<V, wide, 2>;
+            return launch(kern, (n + per - 1) / per, s, n, p, (V*)r, (const V*)Ap, (const V*)pap_partial, n_partial, (V*)scal2, flags2,
+                          parity, (V)eps, g.lpr, g.rpp, groups, (V*)rr_partial);
+        });
+    });
 }
 
 int tsgu_cg2_direction(int vtype, int64_t n, int64_t p, const void* r, void* pvec, void* x, const void* rr_partial, int64_t n_partial,
@@ -694,27 +628,15 @@ int tsgu_cg2_direction(int vtype, int64_t n, int64_t p, const void* r, void* pve
     if (n_partial > 1024) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_BODY                                                                                                          \
-    {                                                                                                                      \
-        VecGeom g;                                                                                                         \
-        constexpr int wide = VT<V>::kWide;                                                                                 \
-        if (!(aligned16(r) && aligned16(pvec) && aligned16(x))) return TSGU_ERR_BAD_ARG;                                   \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                                        \
-        if (g.vec == 1)                                                                                                    \
-            hipLaunchKernelGGL((cg_direction_beta_kernel<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p,       \
-                               (const V*)r, (V*)pvec, (V*)x, (const V*)rr_partial, n_partial, (V*)scal2, flags2, parity,   \
-                               (V)eps, (V)stop_updating_after, (V)tolerance, min_iter_index, g.lpr, g.rpp, (V*)hist,       \
-                               n_hist);                                                                                    \
-        else                                                                                                               \
-            hipLaunchKernelGGL((cg_direction_beta_kernel<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, n, p,    \
-                               (const V*)r, (V*)pvec, (V*)x, (const V*)rr_partial, n_partial, (V*)scal2, flags2, parity,   \
-                               (V)eps, (V)stop_updating_after, (V)tolerance, min_iter_index, g.lpr, g.rpp, (V*)hist,       \
-                               n_hist);                                                                                    \
-        return check_launch();                                                                                             \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (!(aligned16(r) && aligned16(pvec) && aligned16(x))) return TSGU_ERR_BAD_ARG;
+        return launch_lanes<V>(n, p, cg_direction_beta_kernel<V, 1>, cg_direction_beta_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (const V*)r, (V*)pvec, (V*)x, (const V*)rr_partial, n_partial, (V*)scal2, flags2, parity,
+                          (V)eps, (V)stop_updating_after, (V)tolerance, min_iter_index, g.lpr, g.rpp, (V*)hist, n_hist);
+        });
+    });
 }
 
 }  // extern "C"

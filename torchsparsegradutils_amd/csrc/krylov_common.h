@@ -1,5 +1,11 @@
-// Shared pieces of the Krylov kernels (CG in krylov.hip, BiCGSTAB in bicgstab.hip): lane layout for
-// contiguous [n][p] arrays, deterministic block-level column sums, the partial-row fold kernel.
+// Shared pieces of the Krylov kernels (CG in krylov.hip, BiCGSTAB in bicgstab.hip, MINRES in minres.hip): lane layout for
+// contiguous [n][p] arrays, deterministic block-level column sums, the partial-row fold kernel, and the host launch helpers
+// every entry point of the three files is written on:
+//   with_value_type(vtype, f)        calls the generic lambda f with a float or a double tag (`using V = decltype(tag)`)
+//   launch(kern, blocks, s, args...) one kernel on `blocks` workgroups of kBlock threads, then check_launch()
+//   launch_lanes<V>(n, p, scalar, wide, go)   geometry of an [n][p] array, then go(instance, geometry) with the scalar-lane or
+//                                    the wide-lane instance of a kernel — its argument list is written once, in `go`
+//   fold_partials<V>(...)            the fold-then-finalise prefix of the single-workgroup scalar kernels
 #pragma once
 
 #include "tsgu_common.h"
@@ -85,18 +91,46 @@ inline bool geom_for(int64_t n, int64_t p, bool aligned, VecGeom& g) {
     return vec_geom(wide, aligned && (p % wide == 0), n, p, g);
 }
 
+// ---- host side -----------------------------------------------------------------------
+// Value-type dispatch of an entry point: f(V{}) for V = float or double.
+template <typename F>
+inline int with_value_type(int vtype, F&& f) {
+    if (vtype == TSGU_F32) return f(float{});
+    if (vtype == TSGU_F64) return f(double{});
+    return TSGU_ERR_BAD_DTYPE;
+}
+
+template <typename Kern, typename... Args>
+inline int launch(Kern* kern, int64_t blocks, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, s, args...);
+    return check_launch();
+}
+
+// The streaming kernels exist in two instances of one signature, <V, 1> (scalar lanes) and <V, VT<V>::kWide> (16-byte lanes;
+// needs 16-byte aligned operands — `aligned` — and p a multiple of the width).  `go(kern, g)` receives the instance that fits
+// and the geometry and launches it: on g.blocks workgroups with g.lpr, g.rpp wherever the kernel wants them, or on a grid of
+// its own derived from g.
+template <typename V, typename Kern, typename Go>
+inline int launch_lanes(int64_t n, int64_t p, Kern* scalar, Kern* wide, Go&& go, bool aligned = true) {
+    VecGeom g;
+    if (!geom_for<V>(n, p, aligned, g)) return TSGU_ERR_TOO_LARGE;
+    return go(g.vec == 1 ? scalar : wide, g);
+}
+
+// Very many partial rows (the K1 epilogue writes one per workgroup) are folded to kFoldRows rows before a single-workgroup
+// finaliser sums them: needs the caller's `fold` buffer and is done when `wanted` and there are more than 4 * kFoldRows rows.
+// `fold_flags`: the stop word the fold kernel honours (NULL: always runs).  Leaves the rows to finalise in (src, rows).
+template <typename V>
+inline int fold_partials(const void* partial, int64_t n_partial, int64_t p, void* fold, bool wanted, const int* fold_flags,
+                         hipStream_t s, const V*& src, int64_t& rows) {
+    src = (const V*)partial;
+    rows = n_partial;
+    if (!(fold != nullptr && wanted && n_partial > 4 * kFoldRows)) return TSGU_OK;
+    const int64_t chunk = (n_partial + kFoldRows - 1) / kFoldRows;
+    if (const int rc = launch(colsum_fold_kernel<V>, kFoldRows, s, src, n_partial, p, chunk, (V*)fold, fold_flags)) return rc;
+    src = (const V*)fold;
+    rows = kFoldRows;
+    return TSGU_OK;
+}
+
 }  // namespace tsgu
-
-#define TSGU_VSWITCH(vtype, CALL_F32, CALL_F64) \
-    do {                                        \
-        if ((vtype) == TSGU_F32) {              \
-            using V = float;                    \
-            CALL_F32;                           \
-        } else if ((vtype) == TSGU_F64) {       \
-            using V = double;                   \
-            CALL_F64;                           \
-        } else {                                \
-            return TSGU_ERR_BAD_DTYPE;          \
-        }                                       \
-    } while (0)
-

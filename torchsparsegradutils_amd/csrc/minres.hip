@@ -249,27 +249,15 @@ int minres_scalar_launch(int vtype, int phase, const void* partial, int64_t n_pa
         return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // one partial set with very many rows (the K1 epilogue writes one row per workgroup): fold it first
-    const bool do_fold = fold != nullptr && phase != kMrStop && n_partial > 4 * kFoldRows;
-    const int64_t chunk = (n_partial + kFoldRows - 1) / kFoldRows;
-#define TSGU_BODY                                                                                                  \
-    {                                                                                                              \
-        const V* src = (const V*)partial;                                                                          \
-        int64_t rows = n_partial;                                                                                  \
-        if (do_fold) {                                                                                             \
-            hipLaunchKernelGGL((colsum_fold_kernel<V>), dim3(kFoldRows), dim3(kBlock), 0, s, src, n_partial, p,    \
-                               chunk, (V*)fold, (const int*)flags);                                                \
-            if (const int rc = check_launch()) return rc;                                                          \
-            src = (const V*)fold;                                                                                  \
-            rows = kFoldRows;                                                                                      \
-        }                                                                                                          \
-        hipLaunchKernelGGL((minres_scalar_kernel<V>), dim3(1), dim3(kBlock), 0, s, phase, src, rows, set_stride, p, \
-                           (V*)scal, flags, (V)eps, (V)tol, (V)shift0, (const V*)shifts, n_shift, (V)value);       \
-        return check_launch();                                                                                     \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        const V* src;
+        int64_t rows;
+        // only a single partial set is folded (STOP reads two per shift)
+        if (const int rc = fold_partials<V>(partial, n_partial, p, fold, phase != kMrStop, flags, s, src, rows)) return rc;
+        return launch(minres_scalar_kernel<V>, 1, s, phase, src, rows, set_stride, p, (V*)scal, flags, (V)eps, (V)tol, (V)shift0,
+                      (const V*)shifts, n_shift, (V)value);
+    });
 }
 
 int minres_vector_launch(int vtype, int which, int64_t n, int64_t p, void* a0, const void* a1, void* a2, const void* a3, void* a4,
@@ -283,28 +271,19 @@ int minres_vector_launch(int vtype, int which, int64_t n, int64_t p, void* a0, c
         return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define TSGU_GO(KERNEL, ...)                                                                                       \
-    do {                                                                                                           \
-        if (g.vec == 1) hipLaunchKernelGGL((KERNEL<V, 1>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<V, wide>), dim3((unsigned)g.blocks), dim3(kBlock), 0, s, __VA_ARGS__);     \
-    } while (0)
-#define TSGU_BODY                                                                                                  \
-    {                                                                                                              \
-        constexpr int wide = VT<V>::kWide;                                                                         \
-        VecGeom g;                                                                                                 \
-        if (!geom_for<V>(n, p, true, g)) return TSGU_ERR_TOO_LARGE;                                                \
-        if (which == 0)                                                                                            \
-            TSGU_GO(minres_lanczos_kernel, n, p, (V*)a0, (const V*)a1, (const V*)a2, (const V*)scal, flags, g.lpr, g.rpp, \
-                    (V*)partial, (V)value);                                                                        \
-        else                                                                                                       \
-            TSGU_GO(minres_update_kernel, n, p, (V*)a0, (const V*)a1, (V*)a2, (const V*)a3, (V*)a4, (const V*)scal, flags, \
-                    g.lpr, g.rpp, (V*)partial, set_stride, with_norms, (V*)qc, n_shift, shift_stride);             \
-        return check_launch();                                                                                     \
-    }
-    TSGU_VSWITCH(vtype, TSGU_BODY, TSGU_BODY);
-#undef TSGU_BODY
-#undef TSGU_GO
-    return TSGU_OK;
+    return with_value_type(vtype, [&](auto tag) -> int {
+        using V = decltype(tag);
+        constexpr int wide = VT<V>::kWide;
+        if (which == 0)
+            return launch_lanes<V>(n, p, minres_lanczos_kernel<V, 1>, minres_lanczos_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+                return launch(kern, g.blocks, s, n, p, (V*)a0, (const V*)a1, (const V*)a2, (const V*)scal, flags, g.lpr, g.rpp,
+                              (V*)partial, (V)value);
+            });
+        return launch_lanes<V>(n, p, minres_update_kernel<V, 1>, minres_update_kernel<V, wide>, [&](auto kern, const VecGeom& g) {
+            return launch(kern, g.blocks, s, n, p, (V*)a0, (const V*)a1, (V*)a2, (const V*)a3, (V*)a4, (const V*)scal, flags, g.lpr, g.rpp,
+                          (V*)partial, set_stride, with_norms, (V*)qc, n_shift, shift_stride);
+        });
+    });
 }
 
 }  // namespace

@@ -178,18 +178,13 @@ def _bicgstab_fused(matmul_closure, rhs, initial_guess, settings: BICGSTABSettin
     flags = torch.zeros(2 + 3 * p, dtype=torch.int32, device=dev)
     part = torch.empty((3, nb, p), dtype=dtype, device=dev)
     fold = torch.empty((lib.tsgu_cg_fold_rows(), p), dtype=dtype, device=dev)
-    stream = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
 
     def scalar(phase, partial, rows, set_stride=0):
-        _be.check(lib.tsgu_bicg_scalar(vt, phase, None if partial is None else partial.data_ptr(), rows, set_stride,
-                                       fold.data_ptr(), scal.data_ptr(), flags.data_ptr(), float(settings.abstol),
-                                       float(settings.reltol), matvec_max, nmv0, p, dev.index, stream()), "tsgu_bicg_scalar")
+        _be.launch("tsgu_bicg_scalar", dev, vt, phase, partial, rows, set_stride, fold, scal, flags, float(settings.abstol),
+                   float(settings.reltol), matvec_max, nmv0, p)
 
     def vector(which, a0, a1, a2, a3=None, a4=None, partial=None, set_stride=0):
-        _be.check(lib.tsgu_bicg_vector(vt, which, n, p, a0.data_ptr(), a1.data_ptr(), a2.data_ptr(),
-                                       None if a3 is None else a3.data_ptr(), None if a4 is None else a4.data_ptr(),
-                                       scal.data_ptr(), flags.data_ptr(), None if partial is None else partial.data_ptr(),
-                                       set_stride, dev.index, stream()), "tsgu_bicg_vector")
+        _be.launch("tsgu_bicg_vector", dev, vt, which, n, p, a0, a1, a2, a3, a4, scal, flags, partial, set_stride)
 
     with torch.cuda.device(dev):
         rr0 = _be.coldot(r0, r0).unsqueeze(0).contiguous()
@@ -218,9 +213,7 @@ def _bicgstab_fused(matmul_closure, rhs, initial_guess, settings: BICGSTABSettin
             if precon is None:
                 vector(3, x, r, s, t, pv, partial=part[0])  # r, x updates, |r|^2 (:227-235)
             else:
-                _be.check(lib.tsgu_bicg_update_x_precond(vt, n, p, x.data_ptr(), r.data_ptr(), s.data_ptr(), t.data_ptr(),
-                                                         q.data_ptr(), z.data_ptr(), scal.data_ptr(), flags.data_ptr(),
-                                                         part[0].data_ptr(), dev.index, stream()), "tsgu_bicg_update_x_precond")
+                _be.launch("tsgu_bicg_update_x_precond", dev, vt, n, p, x, r, s, t, q, z, scal, flags, part[0])
             scalar(5, part[0], nb)                  # stop tests (:239-241)
 
         done = bool(flags[0].item())

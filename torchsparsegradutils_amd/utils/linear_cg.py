@@ -140,10 +140,9 @@ def linear_cg(
     if (n_iter > 0 and n_tridiag and preconditioner is None and TWO_LAUNCH and p <= 256 and isinstance(op, SparseOperator) and op.dtype == dtype
             and rhs.is_cuda):
         # the coefficients of the first n_tridiag_iter iterations are recorded by the fused kernels; the matrices are built afterwards
-        lib = _be.load_library()
-        fused_tridiag = _two_launch_loop(lib, op, rhs_is_zero, result, residual, has_converged, n_iter, max_iter, tolerance, eps,
-                                         stop_updating_after, lambda: torch.cuda.current_stream(dev).cuda_stream,
-                                         n_hist=min(n_tridiag_iter, n_iter), min_iter_floor=min(n_tridiag_iter, max_iter - 1))
+        fused_tridiag = _two_launch_loop(op, rhs_is_zero, result, residual, has_converged, n_iter, max_iter, tolerance, eps,
+                                         stop_updating_after, n_hist=min(n_tridiag_iter, n_iter),
+                                         min_iter_floor=min(n_tridiag_iter, max_iter - 1))
     if fused_tridiag is not None:
         result, residual_norm, k_done, tolerance_reached, hist = fused_tridiag
         # (reference: the iteration that meets the stop rule leaves before its own row is written)
@@ -284,8 +283,7 @@ def _poll_buffers(dev):
     return got
 
 
-def _two_launch_loop(lib, op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tolerance, eps, stop_after, stream, n_hist=0,
-                     min_iter_floor=0):
+def _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tolerance, eps, stop_after, n_hist=0, min_iter_floor=0):
     """The iterations as K1 (+ p'Ap partials) -> tsgu_cg2_residual -> tsgu_cg2_direction (include/tsgu_hip.h): the state an
     iteration reads sits in the half of its parity, what it produces goes to the other half, so no single-workgroup kernel is
     left between the streaming ones.  Returns None when K1 leaves more partial rows than the kernels sum per workgroup (the
@@ -295,7 +293,7 @@ def _two_launch_loop(lib, op, rhs_is_zero, x, r, has_converged, n_iter, max_iter
     n, p = r.shape
     dev, dtype = r.device, r.dtype
     vt = _be.vtype_of(r)
-    nb = lib.tsgu_cg2_num_blocks(vt, n, p)
+    nb = _be.load_library().tsgu_cg2_num_blocks(vt, n, p)
     if nb <= 0:
         return None
     pvec = r.clone()  # curr_conjugate_vec (reference :293)
@@ -310,7 +308,6 @@ def _two_launch_loop(lib, op, rhs_is_zero, x, r, has_converged, n_iter, max_iter
     rr_partial = torch.empty((nb, p), dtype=dtype, device=dev)
     min_iter_index = max(min(10, max_iter - 1), min_iter_floor)
     hist = torch.zeros((n_hist, 2, p), dtype=dtype, device=dev) if n_hist > 0 else None
-    hist_addr = hist.data_ptr() if hist is not None else None
     state = {"parity": 0, "first": (Ap, pap)}
 
     flags_addr = flags.data_ptr()
@@ -323,12 +320,9 @@ def _two_launch_loop(lib, op, rhs_is_zero, x, r, has_converged, n_iter, max_iter
         else:
             # K1 + p'Ap partials (reference :322, :64-65); it does nothing once this half's done word is set
             Ap, pap = op.matmul_with_dot(pvec, skip=flags_addr + 4 * par)
-        s = stream()
-        _be.check(lib.tsgu_cg2_residual(vt, n, p, r.data_ptr(), Ap.data_ptr(), pap.data_ptr(), pap.shape[0], scal.data_ptr(),
-                                        flags_addr, par, eps, rr_partial.data_ptr(), dev.index, s), "tsgu_cg2_residual")
-        _be.check(lib.tsgu_cg2_direction(vt, n, p, r.data_ptr(), pvec.data_ptr(), x.data_ptr(), rr_partial.data_ptr(), nb,
-                                         scal.data_ptr(), flags_addr, par, eps, stop_after, float(tolerance), min_iter_index,
-                                         hist_addr, n_hist, dev.index, s), "tsgu_cg2_direction")
+        _be.launch("tsgu_cg2_residual", dev, vt, n, p, r, Ap, pap, pap.shape[0], scal, flags, par, eps, rr_partial)
+        _be.launch("tsgu_cg2_direction", dev, vt, n, p, r, pvec, x, rr_partial, nb, scal, flags, par, eps, stop_after, float(tolerance),
+                   min_iter_index, hist, n_hist)
         state["parity"] = par ^ 1
 
     # The host polls one chunk BEHIND the device: after queueing chunk j it copies the done words to pinned memory (asynchronously,
@@ -414,9 +408,8 @@ def _fused_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, toleranc
         raise RuntimeError("linear_cg: more than 1024 simultaneous right-hand sides are not supported")
 
     fused_dot = isinstance(op, SparseOperator) and op.dtype == dtype
-    stream = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
     if preconditioner is None and fused_dot and p <= 256 and TWO_LAUNCH:
-        got = _two_launch_loop(lib, op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tolerance, eps, stop_after, stream)
+        got = _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tolerance, eps, stop_after)
         if got is not None:
             return got
 
@@ -444,33 +437,23 @@ def _fused_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, toleranc
             Ap = checked(op(pvec), dtype).contiguous()
             pap = _be.coldot(pvec, Ap).unsqueeze(0)
             n_partial = 1
-        s = stream()
         if n_partial <= 1024 and p <= 256 and pap.is_contiguous():
             # few partial rows (K1 on the plane sweep, or an operator with its own dot): alpha is summed by every workgroup of the
             # update itself — one launch and one single-workgroup kernel less per iteration
-            _be.check(lib.tsgu_cg_update1_alpha(vt, n, p, r.data_ptr(), Ap.data_ptr(), x.data_ptr(), pvec.data_ptr(), pap.data_ptr(),
-                                                n_partial, scal.data_ptr(), flags.data_ptr(), eps, rr_partial.data_ptr(), dev.index, s),
-                      "tsgu_cg_update1_alpha")
+            _be.launch("tsgu_cg_update1_alpha", dev, vt, n, p, r, Ap, x, pvec, pap, n_partial, scal, flags, eps, rr_partial)
         else:
-            _be.check(lib.tsgu_cg_alpha(vt, pap.data_ptr(), n_partial, fold.data_ptr(), scal.data_ptr(), flags.data_ptr(), eps, p,
-                                        dev.index, s), "tsgu_cg_alpha")
-            _be.check(lib.tsgu_cg_update1(vt, n, p, r.data_ptr(), Ap.data_ptr(), x.data_ptr(), pvec.data_ptr(),
-                                          scal.data_ptr(), flags.data_ptr(), rr_partial.data_ptr(), dev.index, s),
-                      "tsgu_cg_update1")
+            _be.launch("tsgu_cg_alpha", dev, vt, pap, n_partial, fold, scal, flags, eps, p)
+            _be.launch("tsgu_cg_update1", dev, vt, n, p, r, Ap, x, pvec, scal, flags, rr_partial)
         # iteration index -1: the counter is flags[1] on the device, every iteration is the same launch
         if preconditioner is None:
-            _be.check(lib.tsgu_cg_beta(vt, rr_partial.data_ptr(), nb_upd, scal.data_ptr(), flags.data_ptr(), eps,
-                                       stop_after, float(tolerance), -1, min_iter_index, p, dev.index, s),
-                      "tsgu_cg_beta")
+            _be.launch("tsgu_cg_beta", dev, vt, rr_partial, nb_upd, scal, flags, eps, stop_after, float(tolerance), -1, min_iter_index, p)
             z = r
         else:
             z = checked(preconditioner(r), dtype).contiguous()  # z = M r (reference :80)
             rz = _be.coldot(z, r)
-            _be.check(lib.tsgu_cg_beta_precond(vt, rr_partial.data_ptr(), nb_upd, rz.data_ptr(), 1, scal.data_ptr(), flags.data_ptr(),
-                                               eps, stop_after, float(tolerance), -1, min_iter_index, p, dev.index, s),
-                      "tsgu_cg_beta_precond")
-        _be.check(lib.tsgu_cg_update2(vt, n, p, z.data_ptr(), pvec.data_ptr(), scal.data_ptr(),
-                                      flags.data_ptr(), dev.index, s), "tsgu_cg_update2")
+            _be.launch("tsgu_cg_beta_precond", dev, vt, rr_partial, nb_upd, rz, 1, scal, flags, eps, stop_after, float(tolerance), -1,
+                       min_iter_index, p)
+        _be.launch("tsgu_cg_update2", dev, vt, n, p, z, pvec, scal, flags)
 
     done = False
     k = 0

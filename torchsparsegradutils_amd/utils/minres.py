@@ -222,19 +222,14 @@ def _minres_fused(op, rhs: torch.Tensor, shifts: torch.Tensor, value, precond, e
     flags = torch.zeros(2, dtype=torch.int32, device=dev)
     part = torch.empty((2 * S, nb, p), dtype=dtype, device=dev)
     fold = torch.empty((lib.tsgu_cg_fold_rows(), p), dtype=dtype, device=dev)
-    stream = lambda: torch.cuda.current_stream(dev).cuda_stream  # noqa: E731
 
     def scalar(phase, partial, rows, set_stride=0):
-        _be.check(lib.tsgu_minres_scalar_ms(vt, phase, partial.data_ptr(), rows, set_stride, fold.data_ptr(), scal.data_ptr(),
-                                            flags.data_ptr(), float(eps), float(settings.minres_tolerance), shifts.data_ptr(),
-                                            S, val, p, dev.index, stream()), "tsgu_minres_scalar_ms")
+        _be.launch("tsgu_minres_scalar_ms", dev, vt, phase, partial, rows, set_stride, fold, scal, flags, float(eps),
+                   float(settings.minres_tolerance), shifts, S, val, p)
 
     def vector(which, a0, a1, a2, a3=None, a4=None, qc=None, with_norms=False):
-        _be.check(lib.tsgu_minres_vector_ms(vt, which, n, p, a0.data_ptr(), a1.data_ptr(), a2.data_ptr(),
-                                            None if a3 is None else a3.data_ptr(), None if a4 is None else a4.data_ptr(),
-                                            None if qc is None else qc.data_ptr(), scal.data_ptr(), flags.data_ptr(),
-                                            part.data_ptr(), nb * p, int(with_norms), S, plane, val, dev.index, stream()),
-                  "tsgu_minres_vector_ms")
+        _be.launch("tsgu_minres_vector_ms", dev, vt, which, n, p, a0, a1, a2, a3, a4, qc, scal, flags, part, nb * p, int(with_norms), S, plane,
+                   val)
 
     def iteration(check: bool):
         qp = z[1] if q is None else q[1]
