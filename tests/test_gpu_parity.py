@@ -984,6 +984,64 @@ def test_minres_fused_matches_reference_op_chain(dt, monkeypatch):
     assert torch.equal(xg, xe)
 
 
+@pytest.fixture(scope="module")
+def lap16():
+    z = G.load("cg_lap16.npz")
+    return {k: z[k] for k in ("crow", "col", "val", "B")}
+
+
+@pytest.mark.parametrize("two_launch", [True, False], ids=["two_launch", "four_step"])
+@pytest.mark.parametrize("cap", [203, 206])
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+def test_cg_replay_with_and_without_an_eager_tail_equals_eager(dt, cap, two_launch, lap16, monkeypatch):
+    """11 eager iterations, one capture, then replays of 8: 203 = 11 + 24 * 8 ends on a replay, 206 with three eager iterations
+    after the last one.  Both loop forms (`TWO_LAUNCH` on and off) give the bits of the all-eager solve and count the same iterations."""
+    import sys
+
+    from torchsparsegradutils_amd.utils import LinearCGSettings, _graph, last_solve_info, linear_cg
+
+    monkeypatch.setattr(sys.modules[linear_cg.__module__], "TWO_LAUNCH", two_launch)
+    n = 4096
+    A = torch.sparse_csr_tensor(G.t(lap16["crow"], DEV), G.t(lap16["col"], DEV), G.t(lap16["val"], DEV).to(dt), (n, n))
+    B = G.t(lap16["B"], DEV).to(dt)
+    st = LinearCGSettings(max_cg_iterations=cap, cg_tolerance=1e-30)
+    got = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for min_iters in (64, 0):
+            monkeypatch.setattr(_graph, "MIN_ITERS", min_iters)
+            before = dict(_graph.STATS)
+            x = linear_cg(A, B, settings=st)
+            assert _graph.STATS["captures"] == before["captures"] + (1 if min_iters else 0), _graph.STATS
+            assert _graph.STATS["replays"] - before["replays"] >= (20 if min_iters else 0), _graph.STATS
+            got[min_iters] = (x, last_solve_info("linear_cg")["iterations"])
+    assert torch.equal(got[64][0], got[0][0])
+    assert got[64][1] == got[0][1]
+
+
+@pytest.mark.parametrize("max_iter", [150, 157])
+@pytest.mark.parametrize("dt", [torch.float32, torch.float64])
+def test_minres_replay_with_a_tail_equals_eager(dt, max_iter, lap16, monkeypatch):
+    """max_iter + 2 iterations: one eager chunk of 10, one capture, 14 replays, then a tail of 2 (150) or 9 (157) eager
+    iterations without a stopping test."""
+    from torchsparsegradutils_amd.utils import MINRESSettings, _graph, last_solve_info, minres
+
+    n = 4096
+    A = torch.sparse_csr_tensor(G.t(lap16["crow"], DEV), G.t(lap16["col"], DEV), G.t(lap16["val"], DEV).to(dt), (n, n))
+    B = G.t(lap16["B"], DEV).to(dt)
+    st = MINRESSettings(minres_tolerance=0.0)
+    got = {}
+    for min_iters in (64, 0):
+        monkeypatch.setattr(_graph, "MIN_ITERS", min_iters)
+        before = dict(_graph.STATS)
+        x = minres(A, B, max_iter=max_iter, settings=st)
+        assert _graph.STATS["captures"] == before["captures"] + (1 if min_iters else 0), _graph.STATS
+        assert _graph.STATS["replays"] == before["replays"] + (14 if min_iters else 0), _graph.STATS
+        got[min_iters] = (x, last_solve_info("minres")["iterations"])
+    assert torch.equal(got[64][0], got[0][0])
+    assert got[64][1] == got[0][1] == max_iter + 2
+
+
 def test_generic_solve_double_backward():
     """create_graph=True then a Hessian-vector product vs dense autograd (reference test_sparse_solve.py:391-441)."""
     from torchsparsegradutils_amd.utils import LinearCGSettings, linear_cg

@@ -41,3 +41,46 @@ def capture(body, repeat: int):
 def replay(graph) -> None:
     graph.replay()
     STATS["replays"] += 1
+
+
+def run_chunked(body, poll, chunk, *, bound=None, expected=None, first=None, capture_from=None, capturable=False,
+                snapshot=None, restore=None):
+    """The host schedule of every fused Krylov loop: queue iterations in runs, read the stop word after each run, and
+    once the solve is clearly a long one record ``chunk`` iterations as a hipGraph and replay that.
+
+    ``body(j)`` queues one iteration, ``j`` its position inside the current run; ``poll() -> bool`` is the caller's
+    read of its stop word (iterations queued past the stop are no-ops on the device).  The first run is ``first``
+    iterations (default ``chunk``) and always eager, every later one ``chunk``, all clipped to ``bound`` (None: the
+    device ends the solve).  From ``capture_from`` iterations on (default ``first``), while a whole chunk fits under
+    the bound and ``expected - k >= MIN_ITERS`` (``expected``: iterations the solve may still need, default ``bound``),
+    a ``capturable`` loop makes ONE capture attempt; afterwards a run is a replay when the graph exists and a whole
+    chunk fits, eager otherwise.  ``capturable`` is the caller's promise that the body is only this package's own
+    launches, and includes ``enabled()``.  A refused capture has run the Python of ``body`` but nothing on the
+    device: ``snapshot()`` is taken before the attempt and ``restore(snapshot)`` puts the host's view back.  A chunk
+    that is recorded must leave that view where it was (an even number of buffer swaps).
+    Returns (iterations queued, last poll result)."""
+    first = chunk if first is None else first
+    capture_from = first if capture_from is None else capture_from
+    expected = bound if expected is None else expected
+    k, done, graph = 0, False, None
+    while not done and (bound is None or k < bound):
+        fits = bound is None or k + chunk <= bound
+        if capturable and fits and k >= capture_from and expected - k >= MIN_ITERS:
+            saved = snapshot() if snapshot is not None else None
+            position = iter(range(chunk))
+            graph = capture(lambda: body(next(position)), chunk)
+            capturable = False  # one attempt: what is left only falls
+            if graph is None and restore is not None:
+                restore(saved)
+        if graph is not None and fits:
+            replay(graph)
+            k += chunk
+        else:
+            run = first if k == 0 else chunk
+            if bound is not None:
+                run = min(run, bound - k)
+            for j in range(run):
+                body(j)
+            k += run
+        done = poll()
+    return k, done

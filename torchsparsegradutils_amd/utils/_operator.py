@@ -7,6 +7,9 @@ the K1 HIP kernel (optionally with the fused pᵀ(Ap) epilogue CG needs)."""
 
 from __future__ import annotations
 
+import math
+import threading
+
 import torch
 
 from .. import _backend as _be
@@ -86,3 +89,39 @@ def as_operator(matmul_closure):
     if callable(matmul_closure):
         return matmul_closure
     raise RuntimeError("matmul_closure must be a tensor, or a callable object!")
+
+
+def batch_fold(shape):
+    """Right-hand sides with batch dimensions ``(*batch, n, k)`` are solved as the columns ``(n, batch·k)`` of the 2-D path.
+    Returns ``fold`` (``(*batch, n, k) -> (n, batch·k)``), ``unfold`` (``(..., n, batch·k) -> (..., *batch, n, k)``: leading
+    dimensions, such as the shifts of MINRES, pass through) and ``wrap``, which shows a closure that expects the caller's
+    layout the folded one."""
+    batch_shape = tuple(shape[:-2])
+    n, k = shape[-2:]
+    nb = math.prod(batch_shape)
+
+    def fold(t):
+        return t.reshape(nb, n, k).permute(1, 0, 2).reshape(n, nb * k)
+
+    def unfold(t):
+        lead = tuple(t.shape[:-2])
+        return t.reshape(lead + (n, nb, k)).movedim(-2, -3).reshape(lead + batch_shape + (n, k))
+
+    def wrap(fn):
+        return lambda v: fold(fn(unfold(v)))
+
+    return fold, unfold, wrap
+
+
+class _LastSolve(threading.local):
+    """Diagnostics of each thread's most recent solve, per solver."""
+
+    def __init__(self):
+        self.info = {}
+
+
+LAST_SOLVE = _LastSolve()
+
+
+def record_solve(**info) -> None:
+    LAST_SOLVE.info[info["solver"]] = info

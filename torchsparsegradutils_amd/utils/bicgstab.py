@@ -14,13 +14,11 @@ from __future__ import annotations
 import logging
 from typing import Callable, NamedTuple, Optional, Union
 
-import threading
-
 import torch
 
 from .. import _backend as _be
 from . import _graph
-from ._operator import SparseOperator, as_operator, checked
+from ._operator import LAST_SOLVE, SparseOperator, as_operator, checked, record_solve
 
 ENABLE_FUSED = True  # False: the reference's op chain around the K1 matvec, column by column (tests compare the two)
 _POLL = 4  # iterations enqueued between two reads of the device "all columns finished" word
@@ -194,7 +192,7 @@ def _bicgstab_fused(matmul_closure, rhs, initial_guess, settings: BICGSTABSettin
         v = torch.zeros_like(B)
         s = torch.zeros_like(B)
 
-        def iteration():
+        def iteration(_j):
             scalar(1, None, 0)                      # beta, rho (bicgstab.py:183-184)
             vector(0, pv, r, v)                     # p update (:187-189)
             q = pv if precon is None else precon(pv)  # (:191-194)
@@ -216,34 +214,19 @@ def _bicgstab_fused(matmul_closure, rhs, initial_guess, settings: BICGSTABSettin
                 _be.launch("tsgu_bicg_update_x_precond", dev, vt, n, p, x, r, s, t, q, z, scal, flags, part[0])
             scalar(5, part[0], nb)                  # stop tests (:239-241)
 
-        done = bool(flags[0].item())
+        def finished():
+            return bool(flags[0].item())
+
         k = 0
-        graph = None
-        # user callables (operator or preconditioner) are opaque (may synchronise): never captured
-        try_graph = fused_dot and _graph.enabled() and (precon is None or torch.is_tensor(settings.precon))
-        while not done:
-            if try_graph and graph is None and k >= _GRAPH_AFTER and (matvec_max - nmv0) // 2 - k >= _graph.MIN_ITERS:
-                # still running after _GRAPH_AFTER iterations: record one chunk as a hipGraph and replay it
-                graph = _graph.capture(iteration, _POLL)
-                try_graph = graph is not None
-            if graph is not None:
-                _graph.replay(graph)
-            else:
-                for _ in range(_POLL):
-                    iteration()
-            k += _POLL
-            done = bool(flags[0].item())
-    _INFO.last = {"solver": "bicgstab", "iterations_enqueued": k, "finished": True}
+        if not finished():
+            # no host bound: the device enforces the matvec budget, which here only tells whether a capture still pays.  User
+            # callables (operator or preconditioner) are opaque (may synchronise): never captured
+            k, _ = _graph.run_chunked(iteration, finished, _POLL, expected=(matvec_max - nmv0) // 2, capture_from=_GRAPH_AFTER,
+                                      capturable=fused_dot and _graph.enabled() and (precon is None or torch.is_tensor(settings.precon)))
+    record_solve(solver="bicgstab", iterations_enqueued=k, finished=True)
     return x.squeeze(-1) if is_vector else x
-
-
-class _Info(threading.local):
-    last = None
-
-
-_INFO = _Info()
 
 
 def last_solve_info():
     """Diagnostics of this thread's most recent fused ``bicgstab`` call."""
-    return _INFO.last
+    return LAST_SOLVE.info.get("bicgstab")

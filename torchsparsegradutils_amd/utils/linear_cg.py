@@ -19,6 +19,7 @@ no-ops once it is set, so running ahead is harmless).
 
 from __future__ import annotations
 
+import math
 import os
 import threading
 import warnings
@@ -28,7 +29,7 @@ import torch
 
 from .. import _backend as _be
 from . import _graph
-from ._operator import SparseOperator, as_operator, checked
+from ._operator import LAST_SOLVE, SparseOperator, as_operator, batch_fold, checked, record_solve
 
 ENABLE_FUSED_PRECOND = True  # False: preconditioned solves run the recurrences as tensor ops (tests compare the two)
 _POLL = 8  # iterations enqueued between two reads of the device stop flag
@@ -136,27 +137,28 @@ def linear_cg(
     t_mat = None
     if n_tridiag:
         t_mat = torch.zeros(n_tridiag_iter, n_tridiag_iter, n_tridiag, dtype=dtype, device=dev)
-    fused_tridiag = None
-    if (n_iter > 0 and n_tridiag and preconditioner is None and TWO_LAUNCH and p <= 256 and isinstance(op, SparseOperator) and op.dtype == dtype
-            and rhs.is_cuda):
-        # the coefficients of the first n_tridiag_iter iterations are recorded by the fused kernels; the matrices are built afterwards
-        fused_tridiag = _two_launch_loop(op, rhs_is_zero, result, residual, has_converged, n_iter, max_iter, tolerance, eps,
-                                         stop_updating_after, n_hist=min(n_tridiag_iter, n_iter),
-                                         min_iter_floor=min(n_tridiag_iter, max_iter - 1))
-    if fused_tridiag is not None:
-        result, residual_norm, k_done, tolerance_reached, hist = fused_tridiag
-        # (reference: the iteration that meets the stop rule leaves before its own row is written)
-        rows = min(n_tridiag_iter, k_done - 1 if tolerance_reached else k_done)
-        last_tridiag_iter = _tridiag_from_history(hist, n_tridiag, rows, t_mat)
-    elif n_iter > 0:
-        # (CPU operands: the recurrences as tensor ops — the fused step kernels are the MI355X path)
-        if n_tridiag or (preconditioner is not None and not ENABLE_FUSED_PRECOND) or not rhs.is_cuda:
+    last_tridiag_iter = 0
+    if n_iter > 0:
+        two = None
+        if preconditioner is None and TWO_LAUNCH and p <= 256 and isinstance(op, SparseOperator) and op.dtype == dtype and rhs.is_cuda:
+            # n_tridiag: the coefficients of the first n_tridiag_iter iterations are recorded by the fused kernels; the matrices are
+            # built afterwards
+            two = _two_launch_loop(op, rhs_is_zero, result, residual, has_converged, n_iter, max_iter, tolerance, eps,
+                                   stop_updating_after, n_hist=min(n_tridiag_iter, n_iter) if n_tridiag else 0,
+                                   min_iter_floor=min(n_tridiag_iter, max_iter - 1) if n_tridiag else 0)
+        if two is not None:
+            result, residual_norm, k_done, tolerance_reached, hist = two
+            if n_tridiag:
+                # (reference: the iteration that meets the stop rule leaves before its own row is written)
+                rows = min(n_tridiag_iter, k_done - 1 if tolerance_reached else k_done)
+                last_tridiag_iter = _tridiag_from_history(hist, n_tridiag, rows, t_mat)
+        elif n_tridiag or (preconditioner is not None and not ENABLE_FUSED_PRECOND) or not rhs.is_cuda:
+            # (CPU operands: the recurrences as tensor ops — the fused step kernels are the MI355X path)
             result, residual_norm, k_done, tolerance_reached, last_tridiag_iter = _pcg_loop(
                 op, preconditioner, rhs_is_zero, result, residual, has_converged, n_iter, max_iter, tolerance, eps,
                 stop_updating_after, n_tridiag, n_tridiag_iter, t_mat,
             )
         else:
-            last_tridiag_iter = 0
             result, residual_norm, k_done, tolerance_reached = _fused_loop(
                 op, rhs_is_zero, result, residual, has_converged, n_iter, max_iter, tolerance, eps,
                 stop_updating_after, preconditioner,
@@ -176,8 +178,8 @@ def linear_cg(
             UserWarning,
         )
 
-    _INFO.last = {"solver": "linear_cg", "iterations": int(k_done), "tolerance_reached": bool(tolerance_reached) or n_iter == 0,
-                  "residual_norm": residual_norm.detach().reshape(-1).clone(), "tolerance": float(tolerance)}
+    record_solve(solver="linear_cg", iterations=int(k_done), tolerance_reached=bool(tolerance_reached) or n_iter == 0,
+                 residual_norm=residual_norm.detach().reshape(-1).clone(), tolerance=float(tolerance))
     if settings.verbose_linalg:
         print(f"CG finished after {k_done} iterations; mean normalised residual {float(residual_norm.mean()):.3e} "
               f"(tolerance {tolerance}, reached={bool(tolerance_reached) or n_iter == 0}).")
@@ -191,18 +193,11 @@ def linear_cg(
     return result
 
 
-class _Info(threading.local):
-    last = None
-
-
-_INFO = _Info()
-
-
 def last_solve_info():
     """Diagnostics of this thread's most recent ``linear_cg`` call: iterations executed, whether the tolerance
     was reached and the final rhs-normalised residual norm per column (the device already holds them; the
     reference only offers ``verbose_linalg`` printing, utils/linear_cg.py:273-275)."""
-    return _INFO.last
+    return LAST_SOLVE.info.get("linear_cg")
 
 
 def _batched_rhs(matmul_closure, rhs, n_tridiag, tolerance, eps, stop_updating_after, max_iter, max_tridiag_iter,
@@ -212,20 +207,9 @@ def _batched_rhs(matmul_closure, rhs, n_tridiag, tolerance, eps, stop_updating_a
     ``(n, batch·k)``, and solved by the 2-D path.  A 2-D sparse operator applies to every column alike; any other
     closure sees its own ``(*batch, n, k)`` layout through a reshaping wrapper."""
     batch_shape = tuple(rhs.shape[:-2])
-    n, k = rhs.shape[-2:]
-    nb = 1
-    for d in batch_shape:
-        nb *= d
-
-    def fold(t):      # (*batch, n, k) -> (n, batch*k)
-        return t.reshape(nb, n, k).permute(1, 0, 2).reshape(n, nb * k)
-
-    def unfold(t):    # (n, batch*k) -> (*batch, n, k)
-        return t.reshape(n, nb, k).permute(1, 0, 2).reshape(batch_shape + (n, k))
-
-    def wrap(fn):
-        return lambda v: fold(fn(unfold(v)))
-
+    k = rhs.shape[-1]
+    nb = math.prod(batch_shape)
+    fold, unfold, wrap = batch_fold(rhs.shape)
     if torch.is_tensor(matmul_closure) and matmul_closure.layout in (torch.sparse_csr, torch.sparse_coo):
         op = matmul_closure
     else:
@@ -288,8 +272,8 @@ def _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tol
     iteration reads sits in the half of its parity, what it produces goes to the other half, so no single-workgroup kernel is
     left between the streaming ones.  Returns None when K1 leaves more partial rows than the kernels sum per workgroup (the
     caller then runs the four-step form).  Same recurrences, same stop rule (reference :319-382).  `n_hist` > 0: alpha and beta of
-    the first n_hist iterations are kept ([n_hist][2][p], returned as a fifth value) — what the Lanczos tridiagonal matrices are
-    built from; `min_iter_floor`: no stop before that many iterations (reference :379: not while the matrices are being filled)."""
+    the first n_hist iterations are kept ([n_hist][2][p], the fifth value returned, else None) — what the Lanczos tridiagonal matrices
+    are built from; `min_iter_floor`: no stop before that many iterations (reference :379: not while the matrices are being filled)."""
     n, p = r.shape
     dev, dtype = r.device, r.dtype
     vt = _be.vtype_of(r)
@@ -312,7 +296,7 @@ def _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tol
 
     flags_addr = flags.data_ptr()
 
-    def iteration():
+    def iteration(_j):
         par = state["parity"]
         if state["first"] is not None:
             Ap, pap = state["first"]
@@ -329,46 +313,30 @@ def _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tol
     # behind chunk j in the stream), queues chunk j + 1 and only then waits for the copy of chunk j — the GPU always has the next
     # chunk in its queue (a blocking read per chunk left it idle for a launch + a round trip: ~5 us per iteration at C4).
     # Iterations queued past the end are no-ops on the device (K1 included: `skip`).
-    done = False
-    k = 0
-    graph = None
-    try_graph = _graph.enabled()
     polls = _poll_buffers(dev)
-    pending = None
-    which = 0
+    pending, which, seen_done = None, 0, False
+
+    def poll():
+        nonlocal pending, which, seen_done
+        buf, ev = polls[which]
+        buf.copy_(flags[:2], non_blocking=True)
+        ev.record()
+        if pending is not None:
+            pending[1].synchronize()
+            seen_done = bool(pending[0][0] != 0 or pending[0][1] != 0)
+        pending = polls[which]
+        which ^= 1
+        return seen_done
+
     with torch.cuda.device(dev):
-        while k < n_iter and not done:
-            if try_graph and graph is None and k > min_iter_index and n_iter - k >= _graph.MIN_ITERS:
-                # (an even number of iterations per replay: the parities baked into the captured launches stay right)
-                # (a capture that fails part-way has run nothing on the device: the host's view of the parity must not move either)
-                saved = dict(state)
-                graph = _graph.capture(iteration, _POLL)
-                try_graph = graph is not None
-                if graph is None:
-                    state.update(saved)
-            if graph is not None and k + _POLL <= n_iter:
-                _graph.replay(graph)
-                k += _POLL
-            else:
-                upto = min(n_iter, max(k + _POLL, min_iter_index + 1) if k <= min_iter_index else k + _POLL)
-                for _ in range(k, upto):
-                    iteration()
-                k = upto
-            buf, ev = polls[which]
-            buf.copy_(flags[:2], non_blocking=True)
-            ev.record()
-            if pending is not None:
-                pending[1].synchronize()
-                done = bool(pending[0][0] != 0 or pending[0][1] != 0)
-            pending = polls[which]
-            which ^= 1
+        # (_POLL is even: the parities baked into the captured launches stay right from replay to replay)
+        _graph.run_chunked(iteration, poll, _POLL, bound=n_iter, first=max(_POLL, min_iter_index + 1), capturable=_graph.enabled(),
+                           snapshot=lambda: dict(state), restore=state.update)
         head = flags[:2].tolist()   # (waits for everything queued)
         done = head[0] != 0 or head[1] != 0
     k_done = int(flags[2].item())
     rnorm = scal[4 * p : 5 * p].unsqueeze(0)
-    if n_hist > 0:
-        return x, rnorm, k_done, done, hist
-    return x, rnorm, k_done, done
+    return x, rnorm, k_done, done, hist
 
 
 def _tridiag_from_history(hist: torch.Tensor, n_tridiag: int, rows: int, t_mat: torch.Tensor) -> int:
@@ -408,10 +376,6 @@ def _fused_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, toleranc
         raise RuntimeError("linear_cg: more than 1024 simultaneous right-hand sides are not supported")
 
     fused_dot = isinstance(op, SparseOperator) and op.dtype == dtype
-    if preconditioner is None and fused_dot and p <= 256 and TWO_LAUNCH:
-        got = _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tolerance, eps, stop_after)
-        if got is not None:
-            return got
 
     # device state: scal = [rr | alpha | beta | rnorm], flags = [done, iters, has_converged[p], rhs_is_zero[p]]
     scal = torch.zeros(4 * p, dtype=dtype, device=dev)
@@ -429,7 +393,7 @@ def _fused_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, toleranc
     fold = torch.empty((lib.tsgu_cg_fold_rows(), p), dtype=dtype, device=dev)
     min_iter_index = min(10, max_iter - 1)
 
-    def iteration():
+    def iteration(_j):
         if fused_dot:
             Ap, pap = op.matmul_with_dot(pvec)  # K1 + pᵀAp partials (reference :322, :64-65)
             n_partial = pap.shape[0]
@@ -455,27 +419,11 @@ def _fused_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, toleranc
                        min_iter_index, p)
         _be.launch("tsgu_cg_update2", dev, vt, n, p, z, pvec, scal, flags)
 
-    done = False
-    k = 0
-    graph = None
-    try_graph = fused_dot and preconditioner is None and _graph.enabled()  # user callables are opaque (may synchronise): never captured
     with torch.cuda.device(dev):
-        while k < n_iter and not done:
-            if try_graph and graph is None and k > min_iter_index and n_iter - k >= _graph.MIN_ITERS:
-                # long solves: capture _POLL iterations once as a hipGraph and replay it (one host call per
-                # chunk instead of 6 launches per iteration; finished iterations are device-side no-ops)
-                graph = _graph.capture(iteration, _POLL)
-                try_graph = graph is not None
-            if graph is not None and k + _POLL <= n_iter:
-                _graph.replay(graph)
-                k += _POLL
-            else:
-                upto = min(n_iter, max(k + _POLL, min_iter_index + 1) if k <= min_iter_index else k + _POLL)
-                for _ in range(k, upto):
-                    iteration()
-                k = upto
-            head = flags[:2].tolist()  # the only device→host read: [done, iterations executed]
-            done = head[0] != 0
+        # long solves replay _POLL iterations as a hipGraph (one host call per chunk instead of 6 launches per iteration); user
+        # callables are opaque (may synchronise): never captured.  The poll is the only device→host read.
+        _, done = _graph.run_chunked(iteration, lambda: flags[:2].tolist()[0] != 0, _POLL, bound=n_iter, first=max(_POLL, min_iter_index + 1),
+                                     capturable=fused_dot and preconditioner is None and _graph.enabled())
     k_done = int(flags[1].item())
     rnorm = scal[3 * p : 4 * p].unsqueeze(0)
     return x, rnorm, k_done, done

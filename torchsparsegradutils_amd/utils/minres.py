@@ -14,14 +14,13 @@ stopping test and the shifted-system output layout follow reference ``utils/minr
 
 from __future__ import annotations
 
-import threading
 from typing import Callable, NamedTuple, Optional, Union
 
 import torch
 
 from .. import _backend as _be
 from . import _graph
-from ._operator import SparseOperator, as_operator, checked
+from ._operator import LAST_SOLVE, SparseOperator, as_operator, batch_fold, checked, record_solve
 
 
 ENABLE_FUSED = True  # False: the reference's op chain around the K1 matvec (tests compare the two)
@@ -52,23 +51,12 @@ def minres(
         # stop rule is their mean): the batch is folded into the columns, (n, batch·k), and solved by the 2-D path on the fused
         # kernels.  A 2-D sparse operator applies to every column alike; any other closure (and a preconditioner) sees its own
         # (*batch, n, k) layout through a reshaping wrapper.
-        batch_shape = tuple(rhs.shape[:-2])
-        n, k = rhs.shape[-2:]
-        nb = rhs.numel() // (n * k)
-
-        def fold(t):      # (*batch, n, k) -> (n, batch*k)
-            return t.reshape(nb, n, k).permute(1, 0, 2).reshape(n, nb * k)
-
-        def unfold(t):    # (..., n, batch*k) -> (..., *batch, n, k)
-            lead = tuple(t.shape[:-2])
-            return t.reshape(lead + (n, nb, k)).movedim(-2, -3).reshape(lead + batch_shape + (n, k))
-
+        fold, unfold, wrap = batch_fold(rhs.shape)
         if torch.is_tensor(matmul_closure) and matmul_closure.dim() == 2 and matmul_closure.layout in (torch.sparse_csr, torch.sparse_coo):
             op2 = matmul_closure
         else:
-            inner = as_operator(matmul_closure)
-            op2 = lambda v: fold(inner(unfold(v)))  # noqa: E731
-        pre = None if preconditioner is None else (lambda v: fold(preconditioner(unfold(v))))
+            op2 = wrap(as_operator(matmul_closure))
+        pre = None if preconditioner is None else wrap(preconditioner)
         return unfold(minres(op2, fold(rhs).contiguous(), eps, shifts, value, max_iter, pre, settings))
     mm = as_operator(matmul_closure)
     precond = (lambda v: v.clone()) if preconditioner is None else preconditioner
@@ -231,7 +219,8 @@ def _minres_fused(op, rhs: torch.Tensor, shifts: torch.Tensor, value, precond, e
         _be.launch("tsgu_minres_vector_ms", dev, vt, which, n, p, a0, a1, a2, a3, a4, qc, scal, flags, part, nb * p, int(with_norms), S, plane,
                    val)
 
-    def iteration(check: bool):
+    def iteration(j):
+        check = j == 9                                           # every 10th iteration (minres.py:299-305): the last of a whole chunk
         qp = z[1] if q is None else q[1]
         if fused_dot:
             prod, pqq = op.matmul_with_dot(qp)                  # A q with <q, A q> partials (minres.py:261-262)
@@ -249,51 +238,23 @@ def _minres_fused(op, rhs: torch.Tensor, shifts: torch.Tensor, value, precond, e
             vector(1, z[0], q[1], w[0], w[1], sol, qc=q[0], with_norms=check)
             q.reverse()
         if check:
-            scalar(2, part, nb, nb * p)                          # every 10th iteration (minres.py:299-305)
+            scalar(2, part, nb, nb * p)
         z.reverse()                                              # the buffer that held z two steps back now holds z_c
         w.reverse()
 
-    def chunk10():
-        for k in range(10):
-            iteration(k == 9)
+    def restore(roles):                                          # a refused capture ran nothing: undo the recorded role swaps
+        z[:], w[:] = roles
 
-    total = max_iter + 2                                         # (minres.py:259)
-    i = 0
-    graph = None
-    try_graph = fused_dot and precond is None and _graph.enabled()  # user callables are opaque: never captured
     with torch.cuda.device(dev):
-        while i < total:
-            if i % 10 == 0 and total - i >= 10:
-                if try_graph and graph is None and i >= 10 and total - i >= _graph.MIN_ITERS:
-                    roles = (z[:], w[:])
-                    graph = _graph.capture(chunk10, 1)           # buffer roles return after an even number of steps
-                    try_graph = graph is not None
-                    if graph is None:
-                        z[:], w[:] = roles                       # nothing executed: undo the recorded role swaps
-                if graph is not None:
-                    _graph.replay(graph)
-                else:
-                    chunk10()
-                i += 10
-                if bool(flags[0].item()):
-                    break
-            else:
-                iteration((i + 1) % 10 == 0)
-                i += 1
-                if i % 10 == 0 and bool(flags[0].item()):
-                    break
-    _INFO.last = {"solver": "minres", "iterations": i, "tolerance_reached": bool(flags[0].item()),
-                  "tolerance": float(settings.minres_tolerance), "shifts": S}
+        # max_iter + 2 iterations (minres.py:259) in chunks of 10, the stopping test closing each whole chunk; buffer roles return
+        # after an even number of steps; user callables are opaque: never captured
+        i, done = _graph.run_chunked(iteration, lambda: bool(flags[0].item()), 10, bound=max_iter + 2,
+                                     capturable=fused_dot and precond is None and _graph.enabled(),
+                                     snapshot=lambda: (z[:], w[:]), restore=restore)
+    record_solve(solver="minres", iterations=i, tolerance_reached=done, tolerance=float(settings.minres_tolerance), shifts=S)
     return sol[:, : n * p].reshape(S, n, p)
-
-
-class _Info(threading.local):
-    last = None
-
-
-_INFO = _Info()
 
 
 def last_solve_info():
     """Diagnostics of this thread's most recent fused ``minres`` call (iterations, stopping test outcome)."""
-    return _INFO.last
+    return LAST_SOLVE.info.get("minres")
