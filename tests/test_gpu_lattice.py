@@ -186,6 +186,41 @@ def be_vtype(dtype):
     return _backend._VTYPE[dtype]
 
 
+def test_large_lds_opt_in_is_per_kernel_instantiation():
+    """Two launch configurations that both take more than 64 KiB of dynamic LDS and differ in their workgroup size are two
+    instantiations of the kernel, each of which has to be allowed its LDS once per device: first, second, first again in one process
+    (an opt-in remembered per function type instead of per instantiation would leave the second launch without it)."""
+    be, lt, pt = _mods()
+    dev = torch.device("cuda:0")
+    n, p = 16 ** 3, 32
+    crow, col = _stencil_csr(16, 16, 16, True, 27)
+    assert col.numel() == 110592
+    g = torch.Generator().manual_seed(16)
+    val, B = torch.randn(col.numel(), generator=g), torch.randn(n, p, generator=g)
+    dense = torch.sparse_csr_tensor(crow.long(), col.long(), val.double(), (n, n)).to_dense()
+    want = (dense @ B.double()).numpy()
+    plan = pt.RowGather(crow.to(dev), col.to(dev), n, n)
+    lp = lref.build_lattice_plan(plan, dims=(1, 16, 16, 16))
+    assert lp is not None
+    vt = be_vtype(torch.float32)
+    picked = []
+    for cand in lt.rank_configs(lp, be.LAT_SPMM, vt, p, 4, be.lattice_lds_bytes, keep=1 << 30):
+        if picked and cand[3] == picked[0].threads:
+            continue
+        cfg = lt.build_config(lp, cand, be.LAT_SPMM, vt, p, 4, be.lattice_lds_bytes, be)
+        if cfg is not None and cfg.lds_bytes > 65536:
+            picked.append(cfg)
+        if len(picked) == 2:
+            break
+    assert len(picked) == 2 and picked[0].threads != picked[1].threads
+    assert picked[0].lds_bytes > 65536 and picked[1].lds_bytes > 65536
+    val_d, B_d = val.to(dev), B.to(dev)
+    for cfg in (picked[0], picked[1], picked[0]):
+        C = be.csr_spmm_lattice(lp, cfg, val_d, B_d)
+        torch.cuda.synchronize()
+        assert G.rel_err(C.cpu().numpy(), want) < 1e-5, (cfg.ty, cfg.tz, cfg.nseg, cfg.threads)
+
+
 def test_two_dimensional_lattice():
     """9-point stencil on a 2-D lattice: handled as planes of ONE line (ny = 1, no y halo)."""
     be, lt, pt = _mods()

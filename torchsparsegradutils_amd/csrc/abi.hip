@@ -5,18 +5,6 @@
 
 #include <cstring>
 
-namespace tsgu {
-int spmm_dispatch_f32(int, const SpmmParams&, int64_t, hipStream_t);
-int spmm_dispatch_f64(int, const SpmmParams&, int64_t, hipStream_t);
-int spmm_dispatch_bf16(int, const SpmmParams&, int64_t, hipStream_t);
-int sddmm_dispatch_f32(int, const SddmmParams&, int64_t, hipStream_t);
-int sddmm_dispatch_f64(int, const SddmmParams&, int64_t, hipStream_t);
-int sddmm_dispatch_bf16(int, const SddmmParams&, int64_t, hipStream_t);
-int coo_sddmm_dispatch_f32(int, const CooSddmmParams&, hipStream_t);
-int coo_sddmm_dispatch_f64(int, const CooSddmmParams&, hipStream_t);
-int coo_sddmm_dispatch_bf16(int, const CooSddmmParams&, hipStream_t);
-}  // namespace tsgu
-
 using namespace tsgu;
 
 // 128-bit content fingerprint of an index array (see include/tsgu_hip.h): position-weighted sums in wrapping 64-bit integer
@@ -201,11 +189,10 @@ int tsgu_index_fingerprint_match(int itype, int64_t n, const void* x, const void
     if (n == 0) return TSGU_OK;
     const int64_t want = (n + 256 * 16 - 1) / (256 * 16);
     const unsigned blocks = (unsigned)(want < 512 ? want : 512);      // (two workgroups per CU: 64 bytes x 512 threads in flight on each)
-    if (itype == TSGU_I32)
-        fingerprint_launch<int32_t>(blocks, s, x, ref, copy, n, out3, hash);
-    else
-        fingerprint_launch<int64_t>(blocks, s, x, ref, copy, n, out3, hash);
-    return check_launch();
+    return with_index_type(itype, [&](auto i) {
+        fingerprint_launch<decltype(i)>(blocks, s, x, ref, copy, n, out3, hash);
+        return check_launch();
+    });
 }
 
 int tsgu_index_fingerprint(int itype, int64_t n, const void* x, void* out2, int accumulate, int device, void* stream) {
@@ -267,12 +254,7 @@ int tsgu_csr_spmm(int vtype, int itype, int64_t n_rows, int64_t n_cols, int64_t 
     P.ldw = ldw;
     P.dot_partial = dot_partial;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (vtype) {
-        case TSGU_F32: return spmm_dispatch_f32(itype, P, batch, s);
-        case TSGU_F64: return spmm_dispatch_f64(itype, P, batch, s);
-        case TSGU_BF16: return spmm_dispatch_bf16(itype, P, batch, s);
-    }
-    return TSGU_ERR_BAD_DTYPE;
+    return with_value_type<float, double, bf16_t>(vtype, [&](auto v) { return spmm_dispatch<decltype(v)>(itype, P, batch, s); });
 }
 
 int tsgu_csr_sddmm(int vtype, int itype, int64_t n_rows, int64_t n_cols, int64_t nnz_per_item,
@@ -311,12 +293,7 @@ int tsgu_csr_sddmm(int vtype, int itype, int64_t n_rows, int64_t n_cols, int64_t
     P.out = out;
     P.alpha = alpha;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (vtype) {
-        case TSGU_F32: return sddmm_dispatch_f32(itype, P, batch, s);
-        case TSGU_F64: return sddmm_dispatch_f64(itype, P, batch, s);
-        case TSGU_BF16: return sddmm_dispatch_bf16(itype, P, batch, s);
-    }
-    return TSGU_ERR_BAD_DTYPE;
+    return with_value_type<float, double, bf16_t>(vtype, [&](auto v) { return sddmm_dispatch<decltype(v)>(itype, P, batch, s); });
 }
 
 int tsgu_coo_sddmm(int vtype, int itype, int64_t nnz, const void* row, const void* col,
@@ -339,12 +316,7 @@ int tsgu_coo_sddmm(int vtype, int itype, int64_t nnz, const void* row, const voi
     P.out = out;
     P.alpha = alpha;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (vtype) {
-        case TSGU_F32: return coo_sddmm_dispatch_f32(itype, P, s);
-        case TSGU_F64: return coo_sddmm_dispatch_f64(itype, P, s);
-        case TSGU_BF16: return coo_sddmm_dispatch_bf16(itype, P, s);
-    }
-    return TSGU_ERR_BAD_DTYPE;
+    return with_value_type<float, double, bf16_t>(vtype, [&](auto v) { return coo_sddmm_dispatch<decltype(v)>(itype, P, s); });
 }
 
 }  // extern "C"

@@ -36,14 +36,7 @@ int tsgu_csr_mm_backward(int vtype, int itype, int64_t n_rows, int64_t n_cols, i
     P.ldo = ldgb;
     P.o_bs = gb_batch_stride;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vtype == TSGU_F32) {
-        if (itype == TSGU_I32) return bwd_launch<float, int32_t>(P, batch, s);
-        if (itype == TSGU_I64) return bwd_launch<float, int64_t>(P, batch, s);
-    } else if (vtype == TSGU_BF16) {
-        if (itype == TSGU_I32) return bwd_launch<bf16_t, int32_t>(P, batch, s);
-        if (itype == TSGU_I64) return bwd_launch<bf16_t, int64_t>(P, batch, s);
-    }
-    return TSGU_ERR_BAD_DTYPE;
+    return with_types<float, bf16_t>(vtype, itype, [&](auto v, auto i) { return bwd_launch<decltype(v), decltype(i)>(P, batch, s); });
 }
 
 }  // extern "C"

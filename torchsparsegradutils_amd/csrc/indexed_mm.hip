@@ -1,15 +1,6 @@
 // gather_mm / segment_mm: the extern "C" entry points (kernels: indexed_mm_impl.h, one instantiation file per value type).
 #include "indexed_mm_impl.h"
 
-namespace tsgu {
-int imm_fwd_dispatch_f32(int, const ImmFwd<float>&, int64_t, hipStream_t);
-int imm_fwd_dispatch_f64(int, const ImmFwd<double>&, int64_t, hipStream_t);
-int imm_fwd_dispatch_bf16(int, const ImmFwd<bf16_t>&, int64_t, hipStream_t);
-int imm_gradb_dispatch_f32(int, const ImmGradB<float>&, int64_t, hipStream_t);
-int imm_gradb_dispatch_f64(int, const ImmGradB<double>&, int64_t, hipStream_t);
-int imm_gradb_dispatch_bf16(int, const ImmGradB<bf16_t>&, int64_t, hipStream_t);
-}  // namespace tsgu
-
 using namespace tsgu;
 
 namespace {
@@ -86,19 +77,11 @@ int tsgu_segment_mm(int vtype, int itype, int64_t n, int64_t d1, int64_t d2, int
     if (max_tiles < (n + kImmBM - 1) / kImmBM + (n_seg < n ? n_seg : n) + 2) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (vtype) {
-        case TSGU_F32:
-            return imm_fwd_dispatch_f32(itype, fwd_params<float>(offsets, tile_ptr, perm, a, lda, b, b_stride0, b_stride1, b_stride2,
-                                                                 out, ldo, n_seg, d1, d2), max_tiles, s);
-        case TSGU_F64:
-            return imm_fwd_dispatch_f64(itype, fwd_params<double>(offsets, tile_ptr, perm, a, lda, b, b_stride0, b_stride1,
-                                                                  b_stride2, out, ldo, n_seg, d1, d2), max_tiles, s);
-        case TSGU_BF16:
-            return imm_fwd_dispatch_bf16(itype, fwd_params<bf16_t>(offsets, tile_ptr, perm, a, lda, b, b_stride0, b_stride1,
-                                                                   b_stride2, out, ldo, n_seg, d1, d2), max_tiles, s);
-        default:
-            return TSGU_ERR_BAD_DTYPE;
-    }
+    return with_value_type<float, double, bf16_t>(vtype, [&](auto v) {
+        using V = decltype(v);
+        return imm_fwd_dispatch<V>(itype, fwd_params<V>(offsets, tile_ptr, perm, a, lda, b, b_stride0, b_stride1, b_stride2, out, ldo, n_seg, d1, d2),
+                                   max_tiles, s);
+    });
 }
 
 int tsgu_segment_mm_grad_b_workspace(int vtype, int64_t n, int64_t n_seg, int64_t d1, int64_t d2, int64_t* chunk_rows,
@@ -130,19 +113,11 @@ int tsgu_segment_mm_grad_b(int vtype, int itype, int64_t n, int64_t d1, int64_t 
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t launched = n > 0 ? max_chunks : 0;
-    switch (vtype) {
-        case TSGU_F32:
-            return imm_gradb_dispatch_f32(itype, gradb_params<float>(offsets, chunk_ptr, part_ptr, perm, a, lda, g, ldg, grad_b,
-                                                                     workspace, n_seg, d1, d2, c), launched, s);
-        case TSGU_F64:
-            return imm_gradb_dispatch_f64(itype, gradb_params<double>(offsets, chunk_ptr, part_ptr, perm, a, lda, g, ldg, grad_b,
-                                                                      workspace, n_seg, d1, d2, c), launched, s);
-        case TSGU_BF16:
-            return imm_gradb_dispatch_bf16(itype, gradb_params<bf16_t>(offsets, chunk_ptr, part_ptr, perm, a, lda, g, ldg,
-                                                                       grad_b, workspace, n_seg, d1, d2, c), launched, s);
-        default:
-            return TSGU_ERR_BAD_DTYPE;
-    }
+    return with_value_type<float, double, bf16_t>(vtype, [&](auto v) {
+        using V = decltype(v);
+        return imm_gradb_dispatch<V>(itype, gradb_params<V>(offsets, chunk_ptr, part_ptr, perm, a, lda, g, ldg, grad_b, workspace, n_seg, d1, d2, c),
+                                     launched, s);
+    });
 }
 
 }  // extern "C"

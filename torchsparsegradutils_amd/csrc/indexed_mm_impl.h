@@ -371,4 +371,20 @@ int imm_gradb_launch(const ImmGradB<V>& P, int64_t max_chunks, hipStream_t s) {
     return check_launch();
 }
 
+// One translation unit per value type (indexed_mm_f32 / _f64 / _bf16.hip) instantiates these, and with them the kernels of that type.
+template <typename V>
+int imm_fwd_dispatch(int itype, const ImmFwd<V>& P, int64_t max_tiles, hipStream_t s) {
+    return with_index_type(itype, [&](auto i) { return imm_fwd_launch<V, decltype(i)>(P, max_tiles, s); });
+}
+template <typename V>
+int imm_gradb_dispatch(int itype, const ImmGradB<V>& P, int64_t max_chunks, hipStream_t s) {
+    return with_index_type(itype, [&](auto i) { return imm_gradb_launch<V, decltype(i)>(P, max_chunks, s); });
+}
+extern template int imm_fwd_dispatch<float>(int, const ImmFwd<float>&, int64_t, hipStream_t);
+extern template int imm_fwd_dispatch<double>(int, const ImmFwd<double>&, int64_t, hipStream_t);
+extern template int imm_fwd_dispatch<bf16_t>(int, const ImmFwd<bf16_t>&, int64_t, hipStream_t);
+extern template int imm_gradb_dispatch<float>(int, const ImmGradB<float>&, int64_t, hipStream_t);
+extern template int imm_gradb_dispatch<double>(int, const ImmGradB<double>&, int64_t, hipStream_t);
+extern template int imm_gradb_dispatch<bf16_t>(int, const ImmGradB<bf16_t>&, int64_t, hipStream_t);
+
 }  // namespace tsgu

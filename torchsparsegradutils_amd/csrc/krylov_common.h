@@ -1,8 +1,9 @@
 // Shared pieces of the Krylov kernels (CG in krylov.hip, BiCGSTAB in bicgstab.hip, MINRES in minres.hip): lane layout for
 // contiguous [n][p] arrays, deterministic block-level column sums, the partial-row fold kernel, and the host launch helpers
-// every entry point of the three files is written on:
+// every entry point of the three files is written on.  From tsgu_common.h, shared with every other kernel family:
 //   with_value_type(vtype, f)        calls the generic lambda f with a float or a double tag (`using V = decltype(tag)`)
 //   launch(kern, blocks, s, args...) one kernel on `blocks` workgroups of kBlock threads, then check_launch()
+// and here:
 //   launch_lanes<V>(n, p, scalar, wide, go)   geometry of an [n][p] array, then go(instance, geometry) with the scalar-lane or
 //                                    the wide-lane instance of a kernel — its argument list is written once, in `go`
 //   fold_partials<V>(...)            the fold-then-finalise prefix of the single-workgroup scalar kernels
@@ -92,20 +93,6 @@ inline bool geom_for(int64_t n, int64_t p, bool aligned, VecGeom& g) {
 }
 
 // ---- host side -----------------------------------------------------------------------
-// Value-type dispatch of an entry point: f(V{}) for V = float or double.
-template <typename F>
-inline int with_value_type(int vtype, F&& f) {
-    if (vtype == TSGU_F32) return f(float{});
-    if (vtype == TSGU_F64) return f(double{});
-    return TSGU_ERR_BAD_DTYPE;
-}
-
-template <typename Kern, typename... Args>
-inline int launch(Kern* kern, int64_t blocks, hipStream_t s, Args... args) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, s, args...);
-    return check_launch();
-}
-
 // The streaming kernels exist in two instances of one signature, <V, 1> (scalar lanes) and <V, VT<V>::kWide> (16-byte lanes;
 // needs 16-byte aligned operands — `aligned` — and p a multiple of the width).  `go(kern, g)` receives the instance that fits
 // and the geometry and launches it: on g.blocks workgroups with g.lpr, g.rpp wherever the kernel wants them, or on a grid of

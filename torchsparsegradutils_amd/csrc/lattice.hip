@@ -1,12 +1,6 @@
 // Lattice plane-sweep kernels: extern "C" entry points (declared in include/tsgu_hip.h).
 #include "lattice_impl.h"
 
-namespace tsgu {
-int lat_dispatch_f32(int mode, int cl, int threads, const LatParams& P, hipStream_t s);
-int lat_dispatch_bf16(int mode, int cl, int threads, const LatParams& P, hipStream_t s);
-int lat_dispatch_f64(int mode, int cl, int threads, const LatParams& P, hipStream_t s);
-}  // namespace tsgu
-
 using namespace tsgu;
 
 namespace {
@@ -28,7 +22,7 @@ int fill(LatParams& P, const tsgu_lattice_plan* pl, int mode, int vtype, int64_t
     if (cl == 0) return TSGU_ERR_BAD_DTYPE;
     if ((pl->kind != 0) != (mode == kLatSpmmT)) return TSGU_ERR_BAD_ARG;
     if (pl->nb <= 0 || pl->nx <= 0 || pl->ny <= 0 || pl->nz <= 0 || pl->nseg <= 0 || pl->nseg > pl->nx) return TSGU_ERR_BAD_ARG;
-    if ((int64_t)pl->nb * pl->nx * pl->ny * pl->nz != n_rows) return TSGU_ERR_BAD_ARG;
+    if (!lattice_has_rows(*pl, n_rows)) return TSGU_ERR_BAD_ARG;
     if (pl->ry >= pl->ny + (pl->ny == 1) || pl->rz >= pl->nz + (pl->nz == 1)) return TSGU_ERR_BAD_ARG;
     if (pl->threads != 256 && pl->threads != 512 && pl->threads != 1024) return TSGU_ERR_BAD_ARG;
     if (!pl->rec || !pl->lens || !pl->rcls || !pl->wlist || (pl->uniform_len <= 0 && !pl->rstart)) return TSGU_ERR_BAD_ARG;
@@ -43,9 +37,7 @@ int fill(LatParams& P, const tsgu_lattice_plan* pl, int mode, int vtype, int64_t
     if (P.cpl == 2 && (cl < 8 || pl->recw != 28)) return TSGU_ERR_BAD_ARG;
     P.tiles_y = (pl->ny + pl->ty - 1) / pl->ty;
     P.tiles_z = (pl->nz + pl->tz - 1) / pl->tz;
-    P.nseg = pl->nseg;
-    P.seg_len = (pl->nx + pl->nseg - 1) / pl->nseg;
-    if ((int64_t)(P.nseg - 1) * P.seg_len >= pl->nx) return TSGU_ERR_BAD_ARG;   // every segment must own at least one plane
+    if (!split_x(P, *pl)) return TSGU_ERR_BAD_ARG;
     P.ncls = pl->ncls, P.nloc = pl->nloc, P.recw = pl->recw, P.uniform_len = pl->uniform_len;
     P.wlist = static_cast<const unsigned char*>(pl->wlist);
     P.rec = pl->rec;
@@ -55,18 +47,11 @@ int fill(LatParams& P, const tsgu_lattice_plan* pl, int mode, int vtype, int64_t
     P.nnz = nnz;
     const int rc = lat_layout(P, mode, cl, vbytes_of(vtype), pl->threads);
     if (rc < 0) return rc;
-    const int64_t nblocks = (int64_t)P.nb * P.nseg * P.tiles_y * P.tiles_z;
-    if (nblocks > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
-    P.nblocks = nblocks;
-    return TSGU_OK;
+    return set_workgroups(P, (int64_t)P.nb * P.nseg * P.tiles_y * P.tiles_z);
 }
 
 int dispatch(int vtype, int mode, int cl, int threads, const LatParams& P, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vtype == TSGU_F32) return lat_dispatch_f32(mode, cl, threads, P, s);
-    if (vtype == TSGU_BF16) return lat_dispatch_bf16(mode, cl, threads, P, s);
-    if (vtype == TSGU_F64) return lat_dispatch_f64(mode, cl, threads, P, s);
-    return TSGU_ERR_BAD_DTYPE;
+    return with_value_type<float, double, bf16_t>(vtype, [&](auto v) { return lat_dispatch<decltype(v)>(mode, cl, threads, P, static_cast<hipStream_t>(stream)); });
 }
 
 }  // namespace
@@ -93,12 +78,9 @@ static int spmm_lattice(int vtype, const tsgu_lattice_plan* plan, int64_t n_rows
     if (const int rc = fill(P, plan, mode, vtype, p, n_rows, nnz, cl)) return rc;
     if (dot_partial && (mode != kLatSpmm || (vtype != TSGU_F32 && vtype != TSGU_F64) || P.cpl != 1 || dot_rows != P.nblocks)) return TSGU_ERR_BAD_ARG;
     if (n_rows == 0) return TSGU_OK;
-    if (!B || !C || (nnz > 0 && !val) || ldb < p || ldc < p) return TSGU_ERR_BAD_ARG;
-    const int vec = 16 / vbytes_of(vtype);
-    if (ldb % vec || ldc % vec || !aligned16(B) || !aligned16(C)) return TSGU_ERR_BAD_ARG;
+    if ((nnz > 0 && !val) || !lanes_ok({{B, ldb}, {C, ldc}}, p, 16 / vbytes_of(vtype))) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
-    const int64_t plane = (int64_t)plan->ny * plan->nz * vbytes_of(vtype);
-    if (plane * ldb > 0x7fffffffLL || plane * ldc > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+    if (!planes_fit({{B, ldb}, {C, ldc}}, (int64_t)plan->ny * plan->nz * vbytes_of(vtype))) return TSGU_ERR_TOO_LARGE;
     P.val = val;
     P.S = B;
     P.lds_ = ldb;
@@ -129,12 +111,9 @@ int tsgu_csr_sddmm_lattice(int vtype, const tsgu_lattice_plan* plan, int64_t n_r
     int cl = 0;
     if (const int rc = fill(P, plan, kLatSddmm, vtype, p, n_rows, nnz, cl)) return rc;
     if (n_rows == 0 || nnz == 0) return TSGU_OK;
-    if (!R || !Cm || !out_vals || ldr < p || ldc < p) return TSGU_ERR_BAD_ARG;
-    const int vec = 16 / vbytes_of(vtype);
-    if (ldr % vec || ldc % vec || !aligned16(R) || !aligned16(Cm)) return TSGU_ERR_BAD_ARG;
+    if (!out_vals || !lanes_ok({{R, ldr}, {Cm, ldc}}, p, 16 / vbytes_of(vtype))) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
-    const int64_t plane = (int64_t)plan->ny * plan->nz * vbytes_of(vtype);
-    if (plane * ldr > 0x7fffffffLL || plane * ldc > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+    if (!planes_fit({{R, ldr}, {Cm, ldc}}, (int64_t)plan->ny * plan->nz * vbytes_of(vtype))) return TSGU_ERR_TOO_LARGE;
     P.Own = R;
     P.ldown = ldr;
     P.S = Cm;

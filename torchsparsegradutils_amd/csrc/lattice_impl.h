@@ -981,18 +981,7 @@ inline int lat_layout(LatParams& P, int mode, int cl, int vbytes, int nt) {
 
 template <typename V, int CL, int CPL, int MODE, int NT, int NCH>
 int lat_launch_nch(const LatParams& P, hipStream_t stream) {
-    // more than 64 KiB of dynamic LDS has to be allowed once per kernel and device
-    static std::atomic<uint64_t> allowed{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TSGU_ERR_RUNTIME;
-    if (!(allowed.load(std::memory_order_acquire) >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lattice_kernel<V, CL, CPL, MODE, NT, NCH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLatMaxLds) != hipSuccess)
-            return TSGU_ERR_RUNTIME;
-        allowed.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((lattice_kernel<V, CL, CPL, MODE, NT, NCH>), dim3((unsigned)P.nblocks), dim3(NT), (size_t)P.lds_bytes, stream, P);
-    return check_launch();
+    return launch_large_lds<lattice_kernel<V, CL, CPL, MODE, NT, NCH>>(current_device(), P.nblocks, NT, P.lds_bytes, kLatMaxLds, stream, P);
 }
 
 // record widths with an unrolled entry loop: 28 (27-point stencils) and 8 (7-point); anything else loops at run time
@@ -1013,5 +1002,29 @@ int lat_launch_one(const LatParams& P, hipStream_t stream) {
     if (P.recw == 8) return lat_launch_nch<V, CL, 1, MODE, NT, 2>(P, stream);
     return lat_launch_nch<V, CL, 1, MODE, NT, 0>(P, stream);
 }
+
+// One translation unit per value type (lattice_f32 / _f64 / _bf16.hip) instantiates this, and with it the kernels of that type:
+// `threads`, `mode` and `cl` column lanes as template arguments; TSGU_ERR_BAD_ARG when there is no kernel for them.
+template <typename V>
+int lat_dispatch(int mode, int cl, int threads, const LatParams& P, hipStream_t s) {
+    if (sizeof(V) == 8 && P.cpl != 1) return TSGU_ERR_BAD_ARG;      // fp64: one chunk per lane
+    int rc = TSGU_ERR_BAD_ARG;
+    dispatch_pow2<256, 1024>(threads, [&](auto nt) {
+        auto lanes = [&](auto m) {
+            dispatch_pow2<1, 16>(cl, [&](auto c) {
+                constexpr int NT = decltype(nt)::value, MODE = decltype(m)::value, CL = decltype(c)::value;
+                // 16-byte dense rows (4 fp32 columns: the Krylov loops' right-hand sides): the stored-order fp32 product only
+                if constexpr (CL > 1 || (std::is_same<V, float>::value && MODE == kLatSpmm)) rc = lat_launch_one<V, CL, MODE, NT>(P, s);
+            });
+        };
+        if (mode == kLatSpmm) lanes(std::integral_constant<int, kLatSpmm>{});
+        else if (mode == kLatSddmm) lanes(std::integral_constant<int, kLatSddmm>{});
+        else if (mode == kLatSpmmT) lanes(std::integral_constant<int, kLatSpmmT>{});
+    });
+    return rc;
+}
+extern template int lat_dispatch<float>(int, int, int, const LatParams&, hipStream_t);
+extern template int lat_dispatch<double>(int, int, int, const LatParams&, hipStream_t);
+extern template int lat_dispatch<bf16_t>(int, int, int, const LatParams&, hipStream_t);
 
 }  // namespace tsgu

@@ -349,23 +349,14 @@ int tsgu_lattice_rows(int itype, int64_t n_rows, const void* crow, const void* c
     unsigned char* rc_ = static_cast<unsigned char*>(rcls);
     int* st = static_cast<int*>(status);
     const unsigned char* dp = static_cast<const unsigned char*>(disp);
-    if (itype != TSGU_I32 && itype != TSGU_I64) return TSGU_ERR_BAD_DTYPE;
-    if (nd <= 0) {
-        if (itype == TSGU_I32)
-            hipLaunchKernelGGL(lat_rows_kernel<int>, grid, block, 0, s, n_rows, static_cast<const int*>(crow), static_cast<const int*>(col), D, sl,
-                               th, tr, rm, ct, ln, rc_, st, (unsigned)box_mask, periodic);
-        else
-            hipLaunchKernelGGL(lat_rows_kernel<int64_t>, grid, block, 0, s, n_rows, static_cast<const int64_t*>(crow),
-                               static_cast<const int64_t*>(col), D, sl, th, tr, rm, ct, ln, rc_, st, (unsigned)box_mask, periodic);
-    } else {
-        if (itype == TSGU_I32)
-            hipLaunchKernelGGL(lat_trows_kernel<int>, grid, block, 0, s, n_rows, static_cast<const int*>(crow), static_cast<const int*>(col), D,
-                               dp, nd, sl, th, tr, rm, ct, ln, rc_, st);
-        else
-            hipLaunchKernelGGL(lat_trows_kernel<int64_t>, grid, block, 0, s, n_rows, static_cast<const int64_t*>(crow),
-                               static_cast<const int64_t*>(col), D, dp, nd, sl, th, tr, rm, ct, ln, rc_, st);
-    }
-    return check_launch();
+    return with_index_type(itype, [&](auto i) {
+        using I = decltype(i);
+        const I* cr = static_cast<const I*>(crow);
+        const I* cl = static_cast<const I*>(col);
+        if (nd <= 0) hipLaunchKernelGGL(lat_rows_kernel<I>, grid, block, 0, s, n_rows, cr, cl, D, sl, th, tr, rm, ct, ln, rc_, st, (unsigned)box_mask, periodic);
+        else hipLaunchKernelGGL(lat_trows_kernel<I>, grid, block, 0, s, n_rows, cr, cl, D, dp, nd, sl, th, tr, rm, ct, ln, rc_, st);
+        return check_launch();
+    });
 }
 
 int tsgu_lattice_row_codes(int itype, int64_t n_rows, const void* crow, const void* col, int nb, int nx, int ny, int nz, const void* disp,
@@ -378,24 +369,14 @@ int tsgu_lattice_row_codes(int itype, int64_t n_rows, const void* crow, const vo
     const int64_t* rw = static_cast<const int64_t*>(rows);
     int* o = static_cast<int*>(out);
     const unsigned char* dp = static_cast<const unsigned char*>(disp);
-    if (itype != TSGU_I32 && itype != TSGU_I64) return TSGU_ERR_BAD_DTYPE;
-    if (nd <= 0) {
-        if (itype == TSGU_I32)
-            hipLaunchKernelGGL(lat_row_codes_kernel<int>, dim3(nrows), dim3(kLatMaxLen), 0, s, nrows, rw, static_cast<const int*>(crow),
-                               static_cast<const int*>(col), D, o);
-        else
-            hipLaunchKernelGGL(lat_row_codes_kernel<int64_t>, dim3(nrows), dim3(kLatMaxLen), 0, s, nrows, rw, static_cast<const int64_t*>(crow),
-                               static_cast<const int64_t*>(col), D, o);
-    } else {
-        const dim3 grid((unsigned)((nrows + 63) / 64)), block(64);
-        if (itype == TSGU_I32)
-            hipLaunchKernelGGL(lat_trow_codes_kernel<int>, grid, block, 0, s, nrows, rw, static_cast<const int*>(crow),
-                               static_cast<const int*>(col), D, dp, nd, o);
-        else
-            hipLaunchKernelGGL(lat_trow_codes_kernel<int64_t>, grid, block, 0, s, nrows, rw, static_cast<const int64_t*>(crow),
-                               static_cast<const int64_t*>(col), D, dp, nd, o);
-    }
-    return check_launch();
+    return with_index_type(itype, [&](auto i) {
+        using I = decltype(i);
+        const I* cr = static_cast<const I*>(crow);
+        const I* cl = static_cast<const I*>(col);
+        if (nd <= 0) hipLaunchKernelGGL(lat_row_codes_kernel<I>, dim3(nrows), dim3(kLatMaxLen), 0, s, nrows, rw, cr, cl, D, o);
+        else hipLaunchKernelGGL(lat_trow_codes_kernel<I>, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, s, nrows, rw, cr, cl, D, dp, nd, o);
+        return check_launch();
+    });
 }
 
 int tsgu_lattice_block_classes(int64_t n_rows, const void* rcls, int nb, int nx, int ny, int nz, int ty, int tz, int nseg, void* mask,

@@ -557,20 +557,12 @@ inline int linemarch_layout(LineParams& P, int threads, int mode) {
 
 template <int NT, int NZ, int MODE>
 int linemarch_launch_t(const LineParams& P, hipStream_t stream) {
-    static std::atomic<uint64_t> allowed{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TSGU_ERR_RUNTIME;
-    void (*kernel)(const LineParams);
-    if constexpr (MODE == kLatSpmm) kernel = &linemarch_spmm_kernel<NT, NZ>;
-    else if constexpr (MODE == kLatSddmm) kernel = &linemarch_sddmm_kernel<NT, NZ>;
-    else kernel = &linemarch_spmmt_kernel<NT, NZ>;
-    if (!(allowed.load(std::memory_order_acquire) >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLatMaxLds) != hipSuccess)
-            return TSGU_ERR_RUNTIME;
-        allowed.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)P.nblocks), dim3(NT), (size_t)P.lds_bytes, stream, P);
-    return check_launch();
+    auto go = [&](auto kernel) {
+        return launch_large_lds<decltype(kernel)::value>(current_device(), P.nblocks, NT, P.lds_bytes, kLatMaxLds, stream, P);
+    };
+    if constexpr (MODE == kLatSpmm) return go(std::integral_constant<decltype(&linemarch_spmm_kernel<NT, NZ>), &linemarch_spmm_kernel<NT, NZ>>{});
+    else if constexpr (MODE == kLatSddmm) return go(std::integral_constant<decltype(&linemarch_sddmm_kernel<NT, NZ>), &linemarch_sddmm_kernel<NT, NZ>>{});
+    else return go(std::integral_constant<decltype(&linemarch_spmmt_kernel<NT, NZ>), &linemarch_spmmt_kernel<NT, NZ>>{});
 }
 
 }  // namespace tsgu

@@ -48,16 +48,6 @@ int lse_bwd_launch(const LseBwd<V>& P, hipStream_t s) {
     return check_launch();
 }
 
-template <typename F>
-int by_types(int vtype, int itype, F&& f) {
-    if (itype != TSGU_I32 && itype != TSGU_I64) return TSGU_ERR_BAD_DTYPE;
-    const bool i64 = itype == TSGU_I64;
-    if (vtype == TSGU_F32) return i64 ? f(float(), int64_t()) : f(float(), int32_t());
-    if (vtype == TSGU_F64) return i64 ? f(double(), int64_t()) : f(double(), int32_t());
-    if (vtype == TSGU_BF16) return i64 ? f(bf16_t(), int64_t()) : f(bf16_t(), int32_t());
-    return TSGU_ERR_BAD_DTYPE;
-}
-
 }  // namespace
 
 extern "C" {
@@ -82,7 +72,7 @@ int tsgu_segment_logsumexp(int vtype, int itype, int64_t n_groups, int64_t nnz, 
     if (workspace_bytes < need || !aligned16(workspace)) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_types(vtype, itype, [&](auto v, auto i) {
+    return with_types<float, double, bf16_t>(vtype, itype, [&](auto v, auto i) {
         using V = decltype(v);
         using I = decltype(i);
         LseFwd<V> P{};
@@ -110,7 +100,7 @@ int tsgu_segment_logsumexp_backward(int vtype, int itype, int64_t nnz, const voi
     if ((ptr && (!g_grp || !lse_grp || n_groups <= 0)) || (idx && (!g_idx || !lse_idx))) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_types(vtype, itype, [&](auto v, auto i) {
+    return with_types<float, double, bf16_t>(vtype, itype, [&](auto v, auto i) {
         using V = decltype(v);
         using I = decltype(i);
         LseBwd<V> P{};

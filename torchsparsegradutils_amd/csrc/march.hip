@@ -23,7 +23,7 @@ int fill(MarchParams& P, const tsgu_march_plan* pl, int mode, int vtype, int64_t
     if (cl == 0) return TSGU_ERR_BAD_DTYPE;
     if (pl->ntap != 9 || pl->ry != 1 || pl->rz != 1) return TSGU_ERR_BAD_ARG;
     if (pl->nb <= 0 || pl->nx < 3 || pl->ny < 3 || pl->nz < 3 || pl->nseg <= 0 || pl->nseg > pl->nx) return TSGU_ERR_BAD_ARG;
-    if ((int64_t)pl->nb * pl->nx * pl->ny * pl->nz != n_rows) return TSGU_ERR_BAD_ARG;
+    if (!lattice_has_rows(*pl, n_rows)) return TSGU_ERR_BAD_ARG;
     if (pl->mask == 0 || pl->mask >= (1u << 27) || pl->uniform_len < 0 || pl->uniform_len > 27) return TSGU_ERR_BAD_ARG;
     if (pl->uniform_len > 0 ? (int64_t)pl->uniform_len * n_rows != nnz : (pl->rstart == nullptr && pl->mask != kBoxAll)) return TSGU_ERR_BAD_ARG;
     if (pl->mask == kBoxAll && pl->uniform_len == 0) {
@@ -39,9 +39,7 @@ int fill(MarchParams& P, const tsgu_march_plan* pl, int mode, int vtype, int64_t
     P.ty = pl->ty, P.tz = pl->tz, P.ry = pl->ry, P.rz = pl->rz;
     P.tiles_y = (pl->ny + pl->ty - 1) / pl->ty;
     P.tiles_z = (pl->nz + pl->tz - 1) / pl->tz;
-    P.nseg = pl->nseg;
-    P.seg_len = (pl->nx + pl->nseg - 1) / pl->nseg;
-    if ((int64_t)(P.nseg - 1) * P.seg_len >= pl->nx) return TSGU_ERR_BAD_ARG;
+    if (!split_x(P, *pl)) return TSGU_ERR_BAD_ARG;
     P.ncls = pl->ncls, P.ident = pl->ident;
     P.mask = pl->mask;
     P.per_x = pl->periodic & 1, P.per_y = pl->periodic >> 1 & 1, P.per_z = pl->periodic >> 2 & 1;
@@ -61,10 +59,7 @@ int fill(MarchParams& P, const tsgu_march_plan* pl, int mode, int vtype, int64_t
     P.nnz = nnz;
     const int rc = march_layout(P, mode, cl, pl->threads, pl->ntap);
     if (rc < 0) return rc;
-    const int64_t nblocks = (int64_t)P.nb * P.nseg * P.tiles_y * P.tiles_z;
-    if (nblocks > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
-    P.nblocks = nblocks;
-    return TSGU_OK;
+    return set_workgroups(P, (int64_t)P.nb * P.nseg * P.tiles_y * P.tiles_z);
 }
 
 template <int MODE>
@@ -108,8 +103,8 @@ int tsgu_csr_spmm_march(int vtype, const tsgu_march_plan* plan, int transposed, 
         const int lds = linemarch_fill(L, plan, transposed ? kLatSpmmT : kLatSpmm, p, n_rows, nnz);
         if (lds < 0) return lds;
         if (n_rows == 0) return TSGU_OK;
-        if (!B || !C || !val || ldb < p || ldc < p || ldb % 8 || ldc % 8 || !aligned16(B) || !aligned16(C) || !aligned16(val)) return TSGU_ERR_BAD_ARG;
-        if ((int64_t)plan->ny * plan->nz * ldb * 2 > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+        if (!val || !aligned16(val) || !lanes_ok({{B, ldb}, {C, ldc}}, p, 8)) return TSGU_ERR_BAD_ARG;
+        if (!planes_fit({{B, ldb}}, (int64_t)plan->ny * plan->nz * 2)) return TSGU_ERR_TOO_LARGE;
         if (const int rc = set_device(device)) return rc;
         L.val = val, L.S = B, L.lds_ = ldb, L.out = C, L.ldo = ldc;
         return linemarch_run(transposed ? kLatSpmmT : kLatSpmm, L, plan->threads, static_cast<hipStream_t>(stream));
@@ -119,11 +114,9 @@ int tsgu_csr_spmm_march(int vtype, const tsgu_march_plan* plan, int transposed, 
     const int mode = transposed ? kLatSpmmT : kLatSpmm;
     if (const int rc = fill(P, plan, mode, vtype, p, n_rows, nnz, cl)) return rc;
     if (n_rows == 0) return TSGU_OK;
-    if (!B || !C || !val || ldb < p || ldc < p) return TSGU_ERR_BAD_ARG;
-    if (ldb % 4 || ldc % 4 || !aligned16(B) || !aligned16(C)) return TSGU_ERR_BAD_ARG;
+    if (!val || !lanes_ok({{B, ldb}, {C, ldc}}, p, 4)) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
-    const int64_t plane = (int64_t)plan->ny * plan->nz * 4;
-    if (plane * ldb > 0x7fffffffLL || plane * ldc > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+    if (!planes_fit({{B, ldb}, {C, ldc}}, (int64_t)plan->ny * plan->nz * 4)) return TSGU_ERR_TOO_LARGE;
     P.val = val;
     P.S = B;
     P.lds_ = ldb;
@@ -140,8 +133,8 @@ int tsgu_csr_sddmm_march(int vtype, const tsgu_march_plan* plan, int64_t n_rows,
         const int lds = linemarch_fill(L, plan, kLatSddmm, p, n_rows, nnz);
         if (lds < 0) return lds;
         if (n_rows == 0) return TSGU_OK;
-        if (!R || !Cm || !out_vals || ldr < p || ldc < p || ldr % 8 || ldc % 8 || !aligned16(R) || !aligned16(Cm) || !aligned16(out_vals)) return TSGU_ERR_BAD_ARG;
-        if ((int64_t)plan->ny * plan->nz * ldr * 2 > 0x7fffffffLL || (int64_t)plan->ny * plan->nz * ldc * 2 > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+        if (!out_vals || !aligned16(out_vals) || !lanes_ok({{R, ldr}, {Cm, ldc}}, p, 8)) return TSGU_ERR_BAD_ARG;
+        if (!planes_fit({{R, ldr}, {Cm, ldc}}, (int64_t)plan->ny * plan->nz * 2)) return TSGU_ERR_TOO_LARGE;
         if (const int rc = set_device(device)) return rc;
         L.Own = R, L.ldown = ldr, L.S = Cm, L.lds_ = ldc, L.gvals = out_vals, L.alpha = (float)alpha;
         return linemarch_run(kLatSddmm, L, plan->threads, static_cast<hipStream_t>(stream));
@@ -150,11 +143,9 @@ int tsgu_csr_sddmm_march(int vtype, const tsgu_march_plan* plan, int64_t n_rows,
     int cl = 0;
     if (const int rc = fill(P, plan, kLatSddmm, vtype, p, n_rows, nnz, cl)) return rc;
     if (n_rows == 0) return TSGU_OK;
-    if (!R || !Cm || !out_vals || ldr < p || ldc < p) return TSGU_ERR_BAD_ARG;
-    if (ldr % 4 || ldc % 4 || !aligned16(R) || !aligned16(Cm)) return TSGU_ERR_BAD_ARG;
+    if (!out_vals || !lanes_ok({{R, ldr}, {Cm, ldc}}, p, 4)) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
-    const int64_t plane = (int64_t)plan->ny * plan->nz * 4;
-    if (plane * ldr > 0x7fffffffLL || plane * ldc > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+    if (!planes_fit({{R, ldr}, {Cm, ldc}}, (int64_t)plan->ny * plan->nz * 4)) return TSGU_ERR_TOO_LARGE;
     P.Own = R;
     P.ldown = ldr;
     P.S = Cm;

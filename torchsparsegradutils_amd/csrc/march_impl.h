@@ -1137,17 +1137,7 @@ inline int march_layout(MarchParams& P, int mode, int cl, int nt, int ntap) {
 
 template <typename V, int CL, int MODE, int NT, uint32_t MASK, int ROWS>
 int march_launch(const MarchParams& P, hipStream_t stream) {
-    static std::atomic<uint64_t> allowed{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TSGU_ERR_RUNTIME;
-    if (!(allowed.load(std::memory_order_acquire) >> dev & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&march_kernel<V, CL, MODE, NT, 9, MASK, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLatMaxLds) != hipSuccess)
-            return TSGU_ERR_RUNTIME;
-        allowed.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((march_kernel<V, CL, MODE, NT, 9, MASK, ROWS>), dim3((unsigned)P.nblocks), dim3(NT), (size_t)P.lds_bytes, stream, P);
-    return check_launch();
+    return launch_large_lds<march_kernel<V, CL, MODE, NT, 9, MASK, ROWS>>(current_device(), P.nblocks, NT, P.lds_bytes, kLatMaxLds, stream, P);
 }
 
 }  // namespace tsgu

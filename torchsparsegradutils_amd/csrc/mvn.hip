@@ -5,22 +5,6 @@ using namespace tsgu;
 
 namespace {
 
-template <typename F>
-int by_value(int vtype, F&& f) {
-    if (vtype == TSGU_F32) return f(float());
-    if (vtype == TSGU_F64) return f(double());
-    return TSGU_ERR_BAD_DTYPE;      // (bf16 is refused before any launch: the density is offered in fp32 and fp64)
-}
-
-template <typename F>
-int by_types(int vtype, int itype, F&& f) {
-    if (itype != TSGU_I32 && itype != TSGU_I64) return TSGU_ERR_BAD_DTYPE;
-    const bool i64 = itype == TSGU_I64;
-    if (vtype == TSGU_F32) return i64 ? f(float(), int64_t()) : f(float(), int32_t());
-    if (vtype == TSGU_F64) return i64 ? f(double(), int64_t()) : f(double(), int32_t());
-    return TSGU_ERR_BAD_DTYPE;
-}
-
 inline bool grid_ok(int64_t blocks) { return blocks > 0 && blocks <= 0x7fffffffLL; }
 inline int64_t blocks_for(int64_t threads) { return (threads + kBlock - 1) / kBlock; }
 
@@ -49,13 +33,10 @@ int tsgu_csr_diag_positions(int itype, int64_t n_rows, int64_t nnz, const void* 
     if (!grid_ok(blocks)) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (itype == TSGU_I64)
-        hipLaunchKernelGGL((diag_positions_kernel<int64_t>), dim3((unsigned)blocks), dim3(kBlock), 0, s, n_rows, nnz,
-                           (const int64_t*)crow, (const int64_t*)col, (const int64_t*)perm, (int64_t*)pos);
-    else
-        hipLaunchKernelGGL((diag_positions_kernel<int32_t>), dim3((unsigned)blocks), dim3(kBlock), 0, s, n_rows, nnz,
-                           (const int32_t*)crow, (const int32_t*)col, (const int32_t*)perm, (int32_t*)pos);
-    return check_launch();
+    return with_index_type(itype, [&](auto i) {
+        using I = decltype(i);
+        return launch(diag_positions_kernel<I>, blocks, s, n_rows, nnz, (const I*)crow, (const I*)col, (const I*)perm, (I*)pos);
+    });
 }
 
 int tsgu_diag_logsum(int vtype, int itype, int64_t n_rows, int64_t rows_per_item, int64_t n_val, const void* pos,
@@ -70,7 +51,7 @@ int tsgu_diag_logsum(int vtype, int itype, int64_t n_rows, int64_t rows_per_item
     if (items > 65535) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_types(vtype, itype, [&](auto v, auto i) {
+    return with_types(vtype, itype, [&](auto v, auto i) {
         using V = decltype(v);
         using I = decltype(i);
         hipLaunchKernelGGL((diag_logsum_partial_kernel<V, I>), dim3((unsigned)nb, (unsigned)items), dim3(kBlock), 0, s,
@@ -91,7 +72,7 @@ int tsgu_diag_logsum_backward(int vtype, int itype, int64_t n_rows, int64_t rows
     if (!pos && nnz < n_rows) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_types(vtype, itype, [&](auto v, auto i) {
+    return with_types(vtype, itype, [&](auto v, auto i) {
         using V = decltype(v);
         using I = decltype(i);
         if (!pos) {      // dense vector: grad[i] = g[item] / val[i]
@@ -123,7 +104,7 @@ int tsgu_quadform(int vtype, int64_t n, int64_t k, const void* Y, int64_t ldy, i
     if (items > 65535 || col_tiles > 65535) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_value(vtype, [&](auto v) {
+    return with_value_type(vtype, [&](auto v) {
         using V = decltype(v);
         QuadArgs<V> a{static_cast<const V*>(Y), ldy, y_col_stride, static_cast<const V*>(E), lde, e_col_stride,
                       static_cast<const V*>(w), w_mode, k, rows_per_item, mvn_chunk(rows_per_item)};
@@ -145,7 +126,7 @@ int tsgu_quadform_backward(int vtype, int64_t n, int64_t k, const void* Y, int64
     if (!grid_ok(blocks)) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_value(vtype, [&](auto v) {
+    return with_value_type(vtype, [&](auto v) {
         using V = decltype(v);
         QuadArgs<V> a{static_cast<const V*>(Y), ldy, y_col_stride, static_cast<const V*>(E), lde, e_col_stride,
                       static_cast<const V*>(w), w_mode, k, rows_per_item, 0};
@@ -165,7 +146,7 @@ int tsgu_csr_row_sumsq(int vtype, int itype, int64_t n_rows, int64_t nnz, int64_
     if (!grid_ok(blocks)) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_types(vtype, itype, [&](auto v, auto i) {
+    return with_types(vtype, itype, [&](auto v, auto i) {
         using V = decltype(v);
         using I = decltype(i);
         hipLaunchKernelGGL((row_sumsq_kernel<V, I>), dim3((unsigned)blocks), dim3(kBlock), 0, s, n_rows, nnz, n_w,
@@ -185,7 +166,7 @@ int tsgu_csr_row_sumsq_backward(int vtype, int itype, int64_t n_rows, int64_t nn
     if (!grid_ok(blocks)) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return by_types(vtype, itype, [&](auto v, auto i) {
+    return with_types(vtype, itype, [&](auto v, auto i) {
         using V = decltype(v);
         using I = decltype(i);
         hipLaunchKernelGGL((row_sumsq_bwd_kernel<V, I>), dim3((unsigned)blocks), dim3(kBlock), 0, s, n_rows, nnz, n_w,

@@ -1,11 +1,6 @@
 // Row-pair gather kernels: extern "C" entry points (declared in include/tsgu_hip.h).
 #include "rowpack_impl.h"
 
-namespace tsgu {
-int rp_dispatch_f32(int mode, bool perm, int itype, const RpParams& P, hipStream_t s);
-int rp_dispatch_bf16(int mode, bool perm, int itype, const RpParams& P, hipStream_t s);
-}  // namespace tsgu
-
 using namespace tsgu;
 
 namespace {
@@ -40,10 +35,7 @@ int fill(RpParams& P, int64_t n_rows, int64_t n_src, int64_t nnz, int64_t p, con
 }
 
 int dispatch(int vtype, int mode, bool perm, int itype, const RpParams& P, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vtype == TSGU_F32) return rp_dispatch_f32(mode, perm, itype, P, s);
-    if (vtype == TSGU_BF16) return rp_dispatch_bf16(mode, perm, itype, P, s);
-    return TSGU_ERR_BAD_DTYPE;
+    return with_value_type<float, bf16_t>(vtype, [&](auto v) { return rp_dispatch<decltype(v)>(mode, perm, itype, P, static_cast<hipStream_t>(stream)); });
 }
 
 }  // namespace
@@ -53,13 +45,8 @@ extern "C" {
 int tsgu_rowpack_geometry(int vtype, int64_t p, int* rows_per_block, int* entry_lanes, int* max_entries, int* max_union,
                           int* lds_budget_bytes) {
     int cl = 0, ep = 0;
-    if (vtype == TSGU_F32) {
-        if (!rp_geom<float>(p, cl, ep)) return TSGU_ERR_BAD_DTYPE;
-    } else if (vtype == TSGU_BF16) {
-        if (!rp_geom<bf16_t>(p, cl, ep)) return TSGU_ERR_BAD_DTYPE;
-    } else {
-        return TSGU_ERR_BAD_DTYPE;
-    }
+    if (const int rc = with_value_type<float, bf16_t>(vtype, [&](auto v) { return rp_geom<decltype(v)>(p, cl, ep) ? TSGU_OK : TSGU_ERR_BAD_DTYPE; }))
+        return rc;
     if (rows_per_block) *rows_per_block = 2 * (kBlock / (cl * ep));
     if (entry_lanes) *entry_lanes = ep;
     if (max_entries) *max_entries = kRpMaxQ * kBlock;

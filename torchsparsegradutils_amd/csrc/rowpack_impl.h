@@ -457,45 +457,38 @@ int rp_launch(RpParams P, hipStream_t stream) {
     // 32-bit byte offsets into the gathered operand: rows < 2^24, row pitch < 2^24 bytes, whole operand < 4 GiB
     const int64_t pitch = P.lds_ * (int64_t)sizeof(V);
     const bool small = P.n_src < (1ll << 24) && pitch < (1ll << 24) && P.n_src * pitch < (1ll << 32);
-#define TSGU_RP_GO(CLV, EPV, SL, RG)                                                                                          \
-    do {                                                                                                                     \
-        if (small) hipLaunchKernelGGL((csr_rowpack_kernel<V, I, CLV, EPV, MODE, PERM, SL, true, RG>), grid, block, lds, stream, P);  \
-        else hipLaunchKernelGGL((csr_rowpack_kernel<V, I, CLV, EPV, MODE, PERM, SL, false, RG>), grid, block, lds, stream, P);       \
-    } while (0)
-    constexpr int MG = TSGU_RP_MINGROUP;
-#define TSGU_RP_EPOF(CLV) ((CLV) >= MG ? 1 : MG / (CLV))
-    if constexpr (PERM) {
-        switch (cl) {
-            case 2: TSGU_RP_GO(2, TSGU_RP_EPOF(2), true, 2); break;
-            case 4: TSGU_RP_GO(4, TSGU_RP_EPOF(4), true, 2); break;
-            case 8: TSGU_RP_GO(8, 1, true, 2); break;
-            case 16: TSGU_RP_GO(16, 1, true, 2); break;
-        }
-    } else {
-        if (slots) {
-            if constexpr (MODE == kRpSddmm) return TSGU_ERR_BAD_ARG;
-            else {
-                switch (cl) {
-                    case 2: TSGU_RP_GO(2, TSGU_RP_EPOF(2), true, 2); break;
-                    case 4: TSGU_RP_GO(4, TSGU_RP_EPOF(4), true, 2); break;
-                    case 8: TSGU_RP_GO(8, 1, true, 2); break;
-                    case 16: TSGU_RP_GO(16, 1, true, 2); break;
-                }
-            }
-        } else if (rg == 4) {
-            // row quads were parity-green but never faster than pairs where it mattered: not compiled any more
-            return TSGU_ERR_BAD_ARG;
-        } else {
-            switch (cl) {
-                case 8: TSGU_RP_GO(8, 1, false, 2); break;
-                case 16: TSGU_RP_GO(16, 1, false, 2); break;
-                default: return TSGU_ERR_BAD_ARG;
-            }
-        }
+    auto go = [&](auto clv, auto sl) {
+        constexpr int CLV = decltype(clv)::value, EPV = CLV >= TSGU_RP_MINGROUP ? 1 : TSGU_RP_MINGROUP / CLV;
+        constexpr bool SL = decltype(sl)::value;
+        if (small) hipLaunchKernelGGL((csr_rowpack_kernel<V, I, CLV, EPV, MODE, PERM, SL, true, 2>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((csr_rowpack_kernel<V, I, CLV, EPV, MODE, PERM, SL, false, 2>), grid, block, lds, stream, P);
+    };
+    if (slots) {      // (PERM implies slots)
+        if constexpr (!PERM && MODE == kRpSddmm) return TSGU_ERR_BAD_ARG;
+        else dispatch_pow2<2, 16>(cl, [&](auto clv) { go(clv, std::true_type{}); });
+    } else if (rg == 4) {
+        // row quads were parity-green but never faster than pairs where it mattered: not compiled any more
+        return TSGU_ERR_BAD_ARG;
+    } else if constexpr (!PERM) {
+        if (!dispatch_pow2<8, 16>(cl, [&](auto clv) { go(clv, std::false_type{}); })) return TSGU_ERR_BAD_ARG;
     }
-#undef TSGU_RP_EPOF
-#undef TSGU_RP_GO
     return check_launch();
 }
+
+// One translation unit per value type (rowpack_f32 / _bf16.hip) instantiates this, and with it the kernels of that type.
+template <typename V>
+int rp_dispatch(int mode, bool perm, int itype, const RpParams& P, hipStream_t s) {
+    return with_index_type(itype, [&](auto i) -> int {
+        using I = decltype(i);
+        switch (mode) {
+            case kRpSpmm: return perm ? rp_launch<V, I, kRpSpmm, true>(P, s) : rp_launch<V, I, kRpSpmm, false>(P, s);
+            case kRpBwd: return rp_launch<V, I, kRpBwd, true>(P, s);
+            case kRpSddmm: return rp_launch<V, I, kRpSddmm, false>(P, s);
+        }
+        return TSGU_ERR_BAD_ARG;
+    });
+}
+extern template int rp_dispatch<float>(int, bool, int, const RpParams&, hipStream_t);
+extern template int rp_dispatch<bf16_t>(int, bool, int, const RpParams&, hipStream_t);
 
 }  // namespace tsgu

@@ -257,4 +257,20 @@ int coo_sddmm_launch(CooSddmmParams P, hipStream_t stream) {
     });
 }
 
+// One translation unit per value type (sddmm_f32 / _f64 / _bf16.hip) instantiates these, and with them the kernels of that type.
+template <typename V>
+int sddmm_dispatch(int itype, const SddmmParams& P, int64_t batch, hipStream_t stream) {
+    return with_index_type(itype, [&](auto i) { return sddmm_launch<V, decltype(i)>(P, batch, stream); });
+}
+template <typename V>
+int coo_sddmm_dispatch(int itype, const CooSddmmParams& P, hipStream_t stream) {
+    return with_index_type(itype, [&](auto i) { return coo_sddmm_launch<V, decltype(i)>(P, stream); });
+}
+extern template int sddmm_dispatch<float>(int, const SddmmParams&, int64_t, hipStream_t);
+extern template int sddmm_dispatch<double>(int, const SddmmParams&, int64_t, hipStream_t);
+extern template int sddmm_dispatch<bf16_t>(int, const SddmmParams&, int64_t, hipStream_t);
+extern template int coo_sddmm_dispatch<float>(int, const CooSddmmParams&, hipStream_t);
+extern template int coo_sddmm_dispatch<double>(int, const CooSddmmParams&, hipStream_t);
+extern template int coo_sddmm_dispatch<bf16_t>(int, const CooSddmmParams&, hipStream_t);
+
 }  // namespace tsgu

@@ -329,26 +329,32 @@ int spmm_launch(SpmmParams P, int64_t batch, hipStream_t stream) {
     if (P.ldb > 0xffffffffLL) return TSGU_ERR_TOO_LARGE;
     return dispatch_geom(g, [&](auto cl, auto ep) -> int {
         constexpr int CL = decltype(cl)::value, EP = decltype(ep)::value;
-        constexpr int W = VT<V>::kWide;
-#define TSGU_SPMM_GO(VECW, DOTF, PERMF)                                                                              \
-    do {                                                                                                             \
-        if (P.rmul > 1)                                                                                              \
-            hipLaunchKernelGGL((csr_spmm_kernel<V, I, VECW, CL, EP, DOTF, PERMF, true>), grid, dim3(kBlock), 0, stream, P);  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((csr_spmm_kernel<V, I, VECW, CL, EP, DOTF, PERMF, false>), grid, dim3(kBlock), 0, stream, P); \
-    } while (0)
-        if (g.vec == 1) {
-            if (dot) TSGU_SPMM_GO(1, true, false);
-            else if (has_perm) TSGU_SPMM_GO(1, false, true);
-            else TSGU_SPMM_GO(1, false, false);
-        } else {
-            if (dot) TSGU_SPMM_GO(W, true, false);
-            else if (has_perm) TSGU_SPMM_GO(W, false, true);
-            else TSGU_SPMM_GO(W, false, false);
-        }
-#undef TSGU_SPMM_GO
+        using Yes = std::true_type;
+        using No = std::false_type;
+        auto go = [&](auto vecw, auto dotf, auto permf) {
+            constexpr int VECW = decltype(vecw)::value;
+            constexpr bool DOTF = decltype(dotf)::value, PERMF = decltype(permf)::value;
+            if (P.rmul > 1) hipLaunchKernelGGL((csr_spmm_kernel<V, I, VECW, CL, EP, DOTF, PERMF, true>), grid, dim3(kBlock), 0, stream, P);
+            else hipLaunchKernelGGL((csr_spmm_kernel<V, I, VECW, CL, EP, DOTF, PERMF, false>), grid, dim3(kBlock), 0, stream, P);
+        };
+        auto lanes = [&](auto vecw) {
+            if (dot) go(vecw, Yes{}, No{});
+            else if (has_perm) go(vecw, No{}, Yes{});
+            else go(vecw, No{}, No{});
+        };
+        if (g.vec == 1) lanes(std::integral_constant<int, 1>{});
+        else lanes(std::integral_constant<int, VT<V>::kWide>{});
         return check_launch();
     });
 }
+
+// One translation unit per value type (spmm_f32 / _f64 / _bf16.hip) instantiates this, and with it the kernels of that type.
+template <typename V>
+int spmm_dispatch(int itype, const SpmmParams& P, int64_t batch, hipStream_t stream) {
+    return with_index_type(itype, [&](auto i) { return spmm_launch<V, decltype(i)>(P, batch, stream); });
+}
+extern template int spmm_dispatch<float>(int, const SpmmParams&, int64_t, hipStream_t);
+extern template int spmm_dispatch<double>(int, const SpmmParams&, int64_t, hipStream_t);
+extern template int spmm_dispatch<bf16_t>(int, const SpmmParams&, int64_t, hipStream_t);
 
 }  // namespace tsgu

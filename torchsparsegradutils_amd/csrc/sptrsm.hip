@@ -175,20 +175,10 @@ int sptrsm_launch(const TrsmParams& P, int n_cu, int wg_per_cu, hipStream_t stre
     TrsmParams Q = P;
     Q.wgc = tiles == 1 ? (int)(blocks < 64 ? blocks : 64) : 1;
     const dim3 grid((unsigned)blocks, (unsigned)tiles, 1);
-#define TSGU_TRSM_CASE(N)                                                                                 \
-    case N:                                                                                               \
-        hipLaunchKernelGGL((sptrsm_syncfree_kernel<V, I, N>), grid, dim3(kBlock), 0, stream, Q);          \
-        break;
-    switch (cl) {
-        TSGU_TRSM_CASE(1)
-        TSGU_TRSM_CASE(2)
-        TSGU_TRSM_CASE(4)
-        TSGU_TRSM_CASE(8)
-        TSGU_TRSM_CASE(16)
-        TSGU_TRSM_CASE(32)
-        TSGU_TRSM_CASE(64)
-    }
-#undef TSGU_TRSM_CASE
+    // (a `cl` outside the list launches nothing)
+    dispatch_pow2<1, 64>(cl, [&](auto n) {
+        hipLaunchKernelGGL((sptrsm_syncfree_kernel<V, I, decltype(n)::value>), grid, dim3(kBlock), 0, stream, Q);
+    });
     return check_launch();
 }
 
@@ -210,13 +200,8 @@ int tsgu_csr_sptrsm(int vtype, int itype, int64_t n, int64_t nnz,
     if (!ptr || !B || !X || !work || (nnz > 0 && (!idx || !val))) return TSGU_ERR_BAD_ARG;
     if (b_col_stride < 1 || ldb < 1 || (b_col_stride == 1 && ldb < p) || ldx < p || B == X) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
-    // compute-unit count per device ordinal: queried once (hipDeviceGetAttribute costs microseconds on every solve)
-    static int cu_cache[64] = {0};
-    int n_cu = device < 64 ? cu_cache[device] : 0;
-    if (n_cu == 0) {
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return TSGU_ERR_RUNTIME;
-        if (device < 64) cu_cache[device] = n_cu;
-    }
+    const int n_cu = device_cu_count(device);
+    if (n_cu == 0) return TSGU_ERR_RUNTIME;
     TrsmParams P{};
     P.n = n;
     P.p = p;
@@ -234,17 +219,9 @@ int tsgu_csr_sptrsm(int vtype, int itype, int64_t n, int64_t nnz,
     P.unit = unit;
     P.timeout_ticks = 400000000LL;  // 4 s at the 100 MHz wall clock
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vtype == TSGU_F32) {
-        if (itype == TSGU_I32) return sptrsm_launch<float, int32_t>(P, n_cu, workgroups_per_cu, s);
-        if (itype == TSGU_I64) return sptrsm_launch<float, int64_t>(P, n_cu, workgroups_per_cu, s);
-    } else if (vtype == TSGU_F64) {
-        if (itype == TSGU_I32) return sptrsm_launch<double, int32_t>(P, n_cu, workgroups_per_cu, s);
-        if (itype == TSGU_I64) return sptrsm_launch<double, int64_t>(P, n_cu, workgroups_per_cu, s);
-    } else if (vtype == TSGU_BF16) {
-        if (itype == TSGU_I32) return sptrsm_launch<bf16_t, int32_t>(P, n_cu, workgroups_per_cu, s);
-        if (itype == TSGU_I64) return sptrsm_launch<bf16_t, int64_t>(P, n_cu, workgroups_per_cu, s);
-    }
-    return TSGU_ERR_BAD_DTYPE;
+    return with_types<float, double, bf16_t>(vtype, itype, [&](auto v, auto i) {
+        return sptrsm_launch<decltype(v), decltype(i)>(P, n_cu, workgroups_per_cu, s);
+    });
 }
 
 }  // extern "C"

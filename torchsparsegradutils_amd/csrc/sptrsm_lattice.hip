@@ -330,20 +330,9 @@ int sptrsm_lattice_launch(TrsmLatParams P, int n_cu, int workgroups, hipStream_t
     const int64_t need = (((int64_t)P.plan.nlines + P.group - 1) / P.group + kTrsmWaves - 1) / kTrsmWaves;
     if (blocks > need) blocks = need;
     const dim3 grid((unsigned)blocks, 1, 1);
-#define TSGU_TL_CASE(N)                                                                                      \
-    case N:                                                                                                  \
-        hipLaunchKernelGGL((sptrsm_lattice_kernel<V, N>), grid, dim3(kBlock), (size_t)lds, stream, P);       \
-        break;
-    switch (cl) {
-        TSGU_TL_CASE(1)
-        TSGU_TL_CASE(2)
-        TSGU_TL_CASE(4)
-        TSGU_TL_CASE(8)
-        TSGU_TL_CASE(16)
-        TSGU_TL_CASE(32)
-        TSGU_TL_CASE(64)
-    }
-#undef TSGU_TL_CASE
+    dispatch_pow2<1, 64>(cl, [&](auto n) {
+        hipLaunchKernelGGL((sptrsm_lattice_kernel<V, decltype(n)::value>), grid, dim3(kBlock), (size_t)lds, stream, P);
+    });
     return check_launch();
 }
 
@@ -369,12 +358,8 @@ int tsgu_csr_sptrsm_lattice(int vtype, const tsgu_trsm_lattice_plan* plan, int64
     if (plan->uniform_len && n * plan->uniform_len > nnz) return TSGU_ERR_BAD_ARG;
     if (b_col_stride < 1 || ldb < 1 || (b_col_stride == 1 && ldb < p) || ldx < p || B == X) return TSGU_ERR_BAD_ARG;
     if (const int rc = set_device(device)) return rc;
-    static int cu_cache[64] = {0};
-    int n_cu = device < 64 ? cu_cache[device] : 0;
-    if (n_cu == 0) {
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return TSGU_ERR_RUNTIME;
-        if (device < 64) cu_cache[device] = n_cu;
-    }
+    const int n_cu = device_cu_count(device);
+    if (n_cu == 0) return TSGU_ERR_RUNTIME;
     TrsmLatParams P{};
     P.plan = *plan;
     P.n = n;
@@ -391,9 +376,7 @@ int tsgu_csr_sptrsm_lattice(int vtype, const tsgu_trsm_lattice_plan* plan, int64
     P.unit = unit;
     P.timeout_ticks = 400000000LL;  // 4 s at the 100 MHz wall clock
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (vtype == TSGU_F32) return sptrsm_lattice_launch<float>(P, n_cu, workgroups, s);
-    if (vtype == TSGU_F64) return sptrsm_lattice_launch<double>(P, n_cu, workgroups, s);
-    return TSGU_ERR_BAD_DTYPE;
+    return with_value_type(vtype, [&](auto v) { return sptrsm_lattice_launch<decltype(v)>(P, n_cu, workgroups, s); });
 }
 
 }  // extern "C"

@@ -7,16 +7,6 @@ using namespace tsgu;
 
 namespace {
 
-int n_cu_of(int device) {
-    static int cache[64] = {0};
-    int n = device < 64 ? cache[device] : 0;
-    if (n == 0) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
-        if (device < 64) cache[device] = n;
-    }
-    return n;
-}
-
 int fill(TileParams& P, const tsgu_tile_plan* pl, int64_t p) {
     if (!pl || pl->n_rows < 0 || pl->n_cols < 0 || pl->nnz < 0 || pl->n_blocks < 0) return TSGU_ERR_BAD_ARG;
     // (max_union is also the tile row the padding of the entry records names — the kernel's zero row: it must be the kernel's own limit)
@@ -45,7 +35,7 @@ int fill(TileParams& P, const tsgu_tile_plan* pl, int64_t p) {
 template <int MODE>
 int launch(const TileParams& P0, int device, hipStream_t s) {
     TileParams P = P0;
-    const int n_cu = n_cu_of(device);
+    const int n_cu = device_cu_count(device);
     if (n_cu <= 0) return TSGU_ERR_RUNTIME;
     // persistent workgroups, two per CU (76 KB of LDS each): neighbouring blocks share tile rows, consecutive workgroups share an
     // XCD's L2 (xcd_chunked_block)
@@ -61,26 +51,18 @@ int launch(const TileParams& P0, int device, hipStream_t s) {
     }();
     P.cyclic = cyclic;
     using L = TileLds<128>;
-    // the opt-in to more than 64 KB of dynamic LDS is a per-DEVICE attribute of the kernel: one bit per (variant, device)
-    static std::atomic<uint64_t> attr_set[6] = {{0}, {0}, {0}, {0}, {0}, {0}};
     if (device < 0 || device >= 64) return TSGU_ERR_BAD_ARG;
-    const bool perm = P.cpos != nullptr;
-    auto go = [&](auto kern, int slot) -> int {
-        if (!(attr_set[slot].load(std::memory_order_acquire) >> device & 1ull)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L::kTotal) != hipSuccess)
-                return TSGU_ERR_RUNTIME;
-            attr_set[slot].fetch_or(1ull << device, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kTileThreads), L::kTotal, s, P);
-        return check_launch();
+    const bool perm = P.cpos != nullptr, wide = P.ncol > 1;
+    auto go = [&](auto permf, auto widef) {
+        constexpr bool PERM = decltype(permf)::value, WIDE = decltype(widef)::value;
+        return launch_large_lds<tile_kernel<float, 8, MODE, PERM, WIDE>>(device, grid, kTileThreads, L::kTotal, L::kTotal, s, P);
     };
-    const bool wide = P.ncol > 1;
+    using Yes = std::true_type;
+    using No = std::false_type;
     if constexpr (MODE == kTileSpmm) {
-        if (perm) return wide ? go(tile_kernel<float, 8, kTileSpmm, true, true>, 0) : go(tile_kernel<float, 8, kTileSpmm, true, false>, 1);
-        return wide ? go(tile_kernel<float, 8, kTileSpmm, false, true>, 2) : go(tile_kernel<float, 8, kTileSpmm, false, false>, 3);
-    } else {
-        return wide ? go(tile_kernel<float, 8, kTileSddmm, false, true>, 4) : go(tile_kernel<float, 8, kTileSddmm, false, false>, 5);
+        if (perm) return wide ? go(Yes{}, Yes{}) : go(Yes{}, No{});
     }
+    return wide ? go(No{}, Yes{}) : go(No{}, No{});
 }
 
 }  // namespace

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/tsgu_hip.h"
@@ -265,6 +267,129 @@ inline int set_device(int device) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- type dispatch of the entry points ---------------------------------------------------
+// Tags go to generic lambdas (`using V = decltype(tag)`).  A family names the value types it is compiled for:
+// with_value_type<float, bf16_t>(vtype, f) calls f(float{}) or f(bf16_t{}); every other code is TSGU_ERR_BAD_DTYPE.
+// Without a list: float and double (the density reductions, the Krylov kernels).
+template <typename V>
+constexpr int vtype_code() {
+    static_assert(std::is_same<V, float>::value || std::is_same<V, double>::value || std::is_same<V, bf16_t>::value, "not a value type");
+    return std::is_same<V, float>::value ? TSGU_F32 : std::is_same<V, double>::value ? TSGU_F64 : TSGU_BF16;
+}
+
+template <typename... Vs, typename F>
+inline int with_value_type(int vtype, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        return with_value_type<float, double>(vtype, f);
+    } else {
+        int rc = TSGU_ERR_BAD_DTYPE;
+        (void)((vtype == vtype_code<Vs>() && (rc = f(Vs{}), true)) || ...);
+        return rc;
+    }
+}
+
+template <typename F>
+inline int with_index_type(int itype, F&& f) {
+    if (itype == TSGU_I32) return f(int32_t{});
+    if (itype == TSGU_I64) return f(int64_t{});
+    return TSGU_ERR_BAD_DTYPE;
+}
+
+// f(V{}, I{})
+template <typename... Vs, typename F>
+inline int with_types(int vtype, int itype, F&& f) {
+    return with_value_type<Vs...>(vtype, [&](auto v) { return with_index_type(itype, [&](auto i) { return f(v, i); }); });
+}
+
+// A run-time power of two as a compile-time tag: f(std::integral_constant<int, N>{}) for the N in {MIN, 2·MIN, ..., MAX} that
+// equals n; false, and no call, when there is none.
+template <int MIN, int MAX, typename F>
+inline bool dispatch_pow2(int n, F&& f) {
+    if (n == MIN) {
+        f(std::integral_constant<int, MIN>{});
+        return true;
+    }
+    if constexpr (2 * MIN <= MAX) return dispatch_pow2<2 * MIN, MAX>(n, f);
+    else return false;
+}
+
+// ---- launches ------------------------------------------------------------------------------
+// One kernel on `blocks` workgroups of kBlock threads, then check_launch().
+template <typename Kern, typename... Args>
+inline int launch(Kern* kern, int64_t blocks, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), 0, s, args...);
+    return check_launch();
+}
+
+inline int current_device() {
+    int dev = -1;
+    return hipGetDevice(&dev) == hipSuccess ? dev : -1;
+}
+
+// A kernel that may take more than 64 KiB of dynamic LDS: the opt-in (up to `max_lds` bytes) is an attribute of the kernel per
+// DEVICE, set once.  The kernel is a template argument, so every kernel instantiation has its own `allowed` word (one bit per
+// device ordinal) — a word per function TYPE would be shared by instantiations of one signature.
+template <auto Kernel, typename Params>
+inline int launch_large_lds(int dev, int64_t grid, int threads, int lds_bytes, int max_lds, hipStream_t s, const Params& P) {
+    static std::atomic<uint64_t> allowed{0};
+    if (dev < 0 || dev >= 64) return TSGU_ERR_RUNTIME;
+    if (!(allowed.load(std::memory_order_acquire) >> dev & 1ull)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess)
+            return TSGU_ERR_RUNTIME;
+        allowed.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(threads), (size_t)lds_bytes, s, P);
+    return check_launch();
+}
+
+// Compute units of a device ordinal, queried once per device (hipDeviceGetAttribute costs microseconds per call); 0 on failure.
+inline int device_cu_count(int device) {
+    static std::atomic<int> cache[64];
+    int n = device >= 0 && device < 64 ? cache[device].load(std::memory_order_relaxed) : 0;
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
+        if (device >= 0 && device < 64) cache[device].store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
+
+// ---- operands of the stencil entry points (lattice.hip, march.hip) ----------------------------
+// A dense operand of p columns that the kernels touch in 16-byte lanes of `vec` elements.
+struct DenseLanes {
+    const void* ptr;
+    int64_t ld;
+};
+inline bool lanes_ok(std::initializer_list<DenseLanes> ops, int64_t p, int vec) {
+    for (const DenseLanes& o : ops)
+        if (!o.ptr || o.ld < p || o.ld % vec || !aligned16(o.ptr)) return false;
+    return true;
+}
+// ... and whose (y, z) plane is addressed with 31-bit byte offsets
+inline bool planes_fit(std::initializer_list<DenseLanes> ops, int64_t plane_bytes) {
+    for (const DenseLanes& o : ops)
+        if (plane_bytes * o.ld > 0x7fffffffLL) return false;
+    return true;
+}
+
+// The lattice geometry of a plan (tsgu_lattice_plan, tsgu_march_plan) and of the parameter blocks filled from it.
+template <typename Plan>
+inline bool lattice_has_rows(const Plan& pl, int64_t n_rows) {
+    return (int64_t)pl.nb * pl.nx * pl.ny * pl.nz == n_rows;
+}
+// nseg segments of seg_len planes along x; false when a segment would own no plane
+template <typename Params, typename Plan>
+inline bool split_x(Params& P, const Plan& pl) {
+    P.nseg = pl.nseg;
+    P.seg_len = (pl.nx + pl.nseg - 1) / pl.nseg;
+    return (int64_t)(P.nseg - 1) * P.seg_len < pl.nx;
+}
+template <typename Params>
+inline int set_workgroups(Params& P, int64_t nblocks) {
+    if (nblocks > 0x7fffffffLL) return TSGU_ERR_TOO_LARGE;
+    P.nblocks = nblocks;
+    return TSGU_OK;
+}
 
 inline int next_pow2(int64_t x) {
     int r = 1;
