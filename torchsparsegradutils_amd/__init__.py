@@ -1,7 +1,8 @@
 """MI355X-native (gfx950) implementation of torchsparsegradutils' sparse hot path.
 
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
-``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``);
+``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
+and ``sparse_softmax`` / ``sparse_log_softmax`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -12,6 +13,7 @@ from .indexed_matmul import GatherMM, SegmentMM, gather_mm, segment_mm
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
+from .sparse_softmax import SparseSoftmax, sparse_log_softmax, sparse_softmax
 from .sparse_solve import (
     SparseGenericSolve,
     SparseTriangularSolve,
@@ -28,6 +30,8 @@ __all__ = [
     "sparse_generic_lstsq",
     "sparse_logsumexp",
     "sparse_bidir_logsumexp",
+    "sparse_softmax",
+    "sparse_log_softmax",
     "SparseGenericLstsq",
     "wait_for_plans",
     "poll_errors",
@@ -35,6 +39,7 @@ __all__ = [
     "SparseTriangularSolve",
     "SparseGenericSolve",
     "SparseLogSumExp",
+    "SparseSoftmax",
     "SegmentMM",
     "GatherMM",
     "linalg_solve_triangular_compat",

@@ -155,6 +155,13 @@ SIGNATURES = {
     "tsgu_csr_row_sumsq_backward": (_int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_softmax.h (same library, same ABI version)
+SIGNATURES_SOFTMAX = {
+    "tsgu_segment_softmax_workspace": (_int, [_int, _i64, ctypes.POINTER(_i64)]),
+    "tsgu_segment_softmax": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_segment_softmax_backward": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -177,7 +184,7 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -731,6 +738,58 @@ def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx, n_
     launch("tsgu_segment_logsumexp_backward", dev, vtype_of(val), itype_of(itp), val.numel(), val, ptr, n_groups, g_grp, lse_grp, idx, g_idx,
            lse_idx, grad)
     return grad
+
+
+SOFTMAX_STAGE_BYTES = 8192       # kLseStageBytes of csrc/logsumexp_impl.h: one wave's range is this many bytes of accumulators
+
+# Launch notes of the segmented softmax (tests): a list to which every call appends (entry, kernels launched).  None = off.
+SOFTMAX_LAUNCHES = None
+
+
+def segment_softmax_range(dtype: torch.dtype) -> int:
+    """Entries of one range of the segmented softmax kernels for value type `dtype` (bf16 accumulates in fp32)."""
+    return SOFTMAX_STAGE_BYTES // (8 if dtype == torch.float64 else 4)
+
+
+def segment_softmax_workspace_bytes(dtype: torch.dtype, nnz: int) -> int:
+    """Workspace bytes the segmented softmax entries need for `nnz` entries of value type `dtype` when groups cross ranges."""
+    out = ctypes.c_int64(0)
+    check(load_library().tsgu_segment_softmax_workspace(_VTYPE[dtype], nnz, ctypes.byref(out)), "tsgu_segment_softmax_workspace")
+    return int(out.value)
+
+
+def _softmax_call(name: str, ptr, perm, operands, n_groups: int, log_form: bool, crossing: bool, out=None):
+    """One segmented softmax entry: operands (one input, or two) -> `out` (a new value array when None).  `crossing`: some group
+    crosses a range boundary of the kernels (known from the pattern) — only then the workspace and the merge / fix-up launches."""
+    first = operands[0]
+    if out is None:
+        out = torch.empty_like(first)
+    dev = require_device(ptr, perm, *operands, out)
+    if perm is not None and perm.dtype != ptr.dtype:
+        raise RuntimeError(f"index dtypes differ: {ptr.dtype} and {perm.dtype}")
+    for t in (*operands, out):
+        if t.dtype != first.dtype or t.shape != first.shape or not t.is_contiguous():
+            raise RuntimeError("the value arrays must be contiguous, of one dtype and one shape")
+    if not ptr.is_contiguous() or (perm is not None and not perm.is_contiguous()) or ptr.numel() != n_groups + 1:
+        raise RuntimeError("ptr (n_groups + 1 entries) and perm must be contiguous")
+    nnz = first.numel()
+    ws = torch.empty(segment_softmax_workspace_bytes(first.dtype, nnz), dtype=torch.uint8, device=dev) if crossing and nnz else None
+    launch(name, dev, vtype_of(first), itype_of(ptr), n_groups, nnz, ptr, perm, *operands, int(bool(log_form)), out, ws,
+           0 if ws is None else ws.numel())
+    if SOFTMAX_LAUNCHES is not None:
+        SOFTMAX_LAUNCHES.append((name, ("main", "merge", "fix") if ws is not None else ("main",) if nnz and n_groups else ()))
+    return out
+
+
+def segment_softmax(ptr, perm, val, n_groups: int, log_form: bool, crossing: bool, out=None):
+    """y[k'] = softmax (or log-softmax) of val over the segments [ptr[g], ptr[g+1]), k' = perm[k] when perm is given: the result
+    is in val's own order."""
+    return _softmax_call("tsgu_segment_softmax", ptr, perm, (val,), n_groups, log_form, crossing, out)
+
+
+def segment_softmax_backward(ptr, perm, y, g, n_groups: int, log_form: bool, crossing: bool, out=None):
+    """gin = y·(g − Σ_group g·y), or g − exp(y)·Σ_group g for the log form, in the values' own order."""
+    return _softmax_call("tsgu_segment_softmax_backward", ptr, perm, (y, g), n_groups, log_form, crossing, out)
 
 
 SEGMENT_MM_TILE_ROWS = 128       # kImmBM of csrc/indexed_mm_impl.h: the row tile of the plans' tile prefix

@@ -146,6 +146,46 @@ def segment_logsumexp_backward(val, ptr, g_grp, lse_grp, idx, g_idx, lse_idx) ->
     return grad.to(val.dtype)
 
 
+def _segment_ids(ptr: torch.Tensor, n_groups: int, nnz: int) -> torch.Tensor:
+    return torch.repeat_interleave(torch.arange(n_groups), (ptr[1:] - ptr[:-1]).to(torch.int64), output_size=nnz)
+
+
+def _from_plan_order(x: torch.Tensor, perm, dtype: torch.dtype) -> torch.Tensor:
+    x = x.to(dtype)
+    return x if perm is None else torch.empty_like(x).index_copy_(0, perm.to(torch.int64), x)
+
+
+def segment_softmax(ptr: torch.Tensor, perm, val: torch.Tensor, n_groups: int, log_form: bool) -> torch.Tensor:
+    """Softmax (or log-softmax) of val over the segments [ptr[g], ptr[g+1]) (entry k of a segment is val[perm[k]] when perm is
+    given), returned in val's own order.  A group whose maximum is not finite (a NaN, a +inf, nothing but -inf) is NaN
+    throughout, as torch.softmax on the group's values.  bf16 values are computed in fp32 and rounded once."""
+    _cpu_only(ptr, perm, val)
+    acc = torch.float32 if val.dtype == torch.bfloat16 else val.dtype
+    v = (val.reshape(-1) if perm is None else val.reshape(-1).index_select(0, perm.to(torch.int64))).to(acc)
+    grp = _segment_ids(ptr, n_groups, v.numel())
+    top = torch.full((n_groups,), float("-inf"), dtype=acc).scatter_reduce(0, grp, v, "amax", include_self=True)
+    top = torch.where(torch.zeros(n_groups, dtype=acc).index_add(0, grp, v.isnan().to(acc)) > 0, float("nan"), top)
+    shift = torch.where(top.isfinite(), top, torch.zeros_like(top))
+    d = v - shift[grp]
+    e = d.exp()
+    total = torch.zeros(n_groups, dtype=acc).index_add(0, grp, e)
+    y = d - total.log()[grp] if log_form else e / total[grp]
+    y = torch.where(top.isfinite()[grp], y, torch.full_like(y, float("nan")))
+    return _from_plan_order(y, perm, val.dtype)
+
+
+def segment_softmax_backward(ptr: torch.Tensor, perm, y: torch.Tensor, g: torch.Tensor, n_groups: int, log_form: bool) -> torch.Tensor:
+    """gin = y·(g − Σ_group g·y), or g − exp(y)·Σ_group g for the log form; y, g and gin in the values' own order."""
+    _cpu_only(ptr, perm, y, g)
+    acc = torch.float32 if y.dtype == torch.bfloat16 else y.dtype
+    pick = (lambda t: t.reshape(-1)) if perm is None else (lambda t: t.reshape(-1).index_select(0, perm.to(torch.int64)))
+    yy, gg = pick(y).to(acc), pick(g).to(acc)
+    grp = _segment_ids(ptr, n_groups, yy.numel())
+    a, b = (gg, yy.exp()) if log_form else (gg * yy, yy)
+    total = torch.zeros(n_groups, dtype=acc).index_add(0, grp, a)
+    return _from_plan_order(a - b * total[grp], perm, y.dtype)
+
+
 def segment_mm(bounds, perm, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """out[perm[i]] = a[perm[i]] @ b[r] for the positions i in [bounds[r], bounds[r + 1]) (perm None: identity); rows outside
     [bounds[0], bounds[-1]) are zeros.  One torch.matmul per segment; `b` may be a transposed view."""
