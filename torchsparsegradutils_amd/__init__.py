@@ -2,7 +2,7 @@
 
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
-and ``sparse_softmax`` / ``sparse_log_softmax`` beside them;
+and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -10,6 +10,7 @@ from ._backend import poll_errors
 from ._compat import linalg_solve_triangular_compat
 from ._pattern import wait_for_plans
 from .indexed_matmul import GatherMM, SegmentMM, gather_mm, segment_mm
+from .sparse_attention import SparseAttention, sparse_attention
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
@@ -32,6 +33,7 @@ __all__ = [
     "sparse_bidir_logsumexp",
     "sparse_softmax",
     "sparse_log_softmax",
+    "sparse_attention",
     "SparseGenericLstsq",
     "wait_for_plans",
     "poll_errors",
@@ -40,6 +42,7 @@ __all__ = [
     "SparseGenericSolve",
     "SparseLogSumExp",
     "SparseSoftmax",
+    "SparseAttention",
     "SegmentMM",
     "GatherMM",
     "linalg_solve_triangular_compat",

@@ -162,6 +162,21 @@ SIGNATURES_SOFTMAX = {
     "tsgu_segment_softmax_backward": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _i64, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_attention.h (same library, same ABI version)
+SIGNATURES_ATTENTION = {
+    "tsgu_csr_attention_supported": (_int, [_int, _int, _int]),
+    "tsgu_csr_attention_geometry": (_int, [_int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_attention": (
+        _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _int, _int, _dbl, _ptr, _i64,
+               _ptr, _int, _ptr]),
+    "tsgu_csr_attention_backward_rows": (
+        _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _int, _int,
+               _dbl, _ptr, _i64, _ptr, _ptr, _int, _ptr]),
+    "tsgu_csr_attention_backward_cols": (
+        _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _int,
+               _int, _dbl, _ptr, _i64, _ptr, _i64, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -184,7 +199,7 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -790,6 +805,85 @@ def segment_softmax(ptr, perm, val, n_groups: int, log_form: bool, crossing: boo
 def segment_softmax_backward(ptr, perm, y, g, n_groups: int, log_form: bool, crossing: bool, out=None):
     """gin = y·(g − Σ_group g·y), or g − exp(y)·Σ_group g for the log form, in the values' own order."""
     return _softmax_call("tsgu_segment_softmax_backward", ptr, perm, (y, g), n_groups, log_form, crossing, out)
+
+
+def attention_supported(dtype: torch.dtype, heads: int, d: int) -> bool:
+    """Do the attention kernels take `heads` heads of width `d` in value type `dtype`?  Host only (no GPU needed)."""
+    vt = _VTYPE.get(dtype)
+    return vt is not None and bool(load_library().tsgu_csr_attention_supported(vt, int(heads), int(d)))
+
+
+def attention_geometry(dtype: torch.dtype, heads: int, d: int):
+    """(entry lanes of a row's lane group, rows per workgroup, entries of one staged slice) of the attention kernels for
+    (dtype, heads, d): the sizes at which their walk changes path.  Host only."""
+    ep, rpb, stage = _int(0), _int(0), _int(0)
+    check(load_library().tsgu_csr_attention_geometry(_VTYPE[dtype], int(heads), int(d), ctypes.byref(ep), ctypes.byref(rpb),
+                                                     ctypes.byref(stage)), "tsgu_csr_attention_geometry")
+    return int(ep.value), int(rpb.value), int(stage.value)
+
+
+def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
+    """A 2-D operand as the attention kernels read it: unit column stride, base and row stride multiples of 16 bytes."""
+    ok = t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and \
+        (t.size(0) <= 1 or (t.stride(0) >= t.size(1) and (t.stride(0) * t.element_size()) % 16 == 0))
+    return t if ok else t.clone(memory_format=torch.contiguous_format)
+
+
+def _attention_walk(walk, bias, *dense):
+    ptr, idx, perm = walk
+    dev = require_device(ptr, idx, perm, bias, *dense)
+    if idx.dtype != ptr.dtype or (perm is not None and perm.dtype != ptr.dtype):
+        raise RuntimeError("the index arrays of a walk must have one dtype")
+    if not (ptr.is_contiguous() and idx.is_contiguous() and (perm is None or perm.is_contiguous())):
+        raise RuntimeError("ptr, idx and perm must be contiguous")
+    if bias is not None and (bias.dtype != dense[0].dtype or not bias.is_contiguous() or bias.numel() != idx.numel()):
+        raise RuntimeError("the bias must be a contiguous value array of the pattern in the operands' dtype")
+    for t in dense:
+        if t.dim() != 2 or t.dtype != dense[0].dtype or t.size(1) != dense[0].size(1):
+            raise RuntimeError("the dense operands must be 2-D [rows, heads*d] of one dtype and width")
+    return dev
+
+
+def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def csr_attention(walk, bias, Q, K, V, heads: int, d: int, scale: float):
+    """(O [n, heads·d], lse [n, heads] in the accumulator type) of attention over the pattern walked by rows as
+    ``walk = (ptr, idx, perm or None)``; bias: the pattern's value array (at perm[k] for entry k) or None."""
+    dev = _attention_walk(walk, bias, Q, K, V)
+    ptr, idx, perm = walk
+    Q, K, V = _aligned_rows(Q), _aligned_rows(K), _aligned_rows(V)
+    n, m = Q.size(0), K.size(0)
+    O = torch.empty((n, heads * d), dtype=Q.dtype, device=dev)
+    lse = torch.empty((n, heads), dtype=_acc_dtype(Q.dtype), device=dev)
+    launch("tsgu_csr_attention", dev, vtype_of(Q), itype_of(ptr), n, m, idx.numel(), ptr, idx, perm, bias, Q, _ld(Q), K, _ld(K),
+           V, _ld(V), heads, d, float(scale), O, _ld(O), lse)
+    return O, lse
+
+
+def csr_attention_backward(walk, twalk, bias, Q, K, V, dO, lse, heads: int, d: int, scale: float, want_dA: bool):
+    """(dQ, dK, dV, dA or None) from the forward's lse: the row pass over `walk`, then the column pass over the transposed walk
+    `twalk` on the same stream.  dA is in the accumulator type, in the order of the pattern's value array."""
+    dev = _attention_walk(walk, bias, Q, K, V, dO)
+    _attention_walk(twalk, bias, Q, K, V, dO)
+    ptr, idx, perm = walk
+    tptr, tidx, tperm = twalk
+    Q, K, V, dO = _aligned_rows(Q), _aligned_rows(K), _aligned_rows(V), _aligned_rows(dO)
+    n, m, nnz = Q.size(0), K.size(0), idx.numel()
+    acc = _acc_dtype(Q.dtype)
+    if lse.dtype != acc or lse.shape != (n, heads) or not lse.is_contiguous():
+        raise RuntimeError("lse must be the forward's [n, heads] array in the accumulator type")
+    dQ, dK, dV = torch.empty_like(Q, memory_format=torch.contiguous_format), torch.empty((m, heads * d), dtype=Q.dtype, device=dev), \
+        torch.empty((m, heads * d), dtype=Q.dtype, device=dev)
+    delta = torch.empty((n, heads), dtype=acc, device=dev)
+    dA = torch.empty((nnz,), dtype=acc, device=dev) if want_dA else None
+    vt, it = vtype_of(Q), itype_of(ptr)
+    launch("tsgu_csr_attention_backward_rows", dev, vt, it, n, m, nnz, ptr, idx, perm, bias, Q, _ld(Q), K, _ld(K), V, _ld(V),
+           dO, _ld(dO), lse, heads, d, float(scale), dQ, _ld(dQ), delta, dA)
+    launch("tsgu_csr_attention_backward_cols", dev, vt, it, n, m, nnz, tptr, tidx, tperm, bias, Q, _ld(Q), K, _ld(K), V,
+           _ld(V), dO, _ld(dO), lse, delta, heads, d, float(scale), dK, _ld(dK), dV, _ld(dV))
+    return dQ, dK, dV, dA
 
 
 SEGMENT_MM_TILE_ROWS = 128       # kImmBM of csrc/indexed_mm_impl.h: the row tile of the plans' tile prefix

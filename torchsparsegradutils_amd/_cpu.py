@@ -20,6 +20,8 @@ column dots of the Krylov loops            :func:`coldot`
 nested-tensor ``segment_mm`` / ``gather_mm``        :func:`segment_mm` / :func:`segment_mm_grad_b`: rows in plan order (a
   indexed_matmul.py:95-105, :203-217       stable argsort of ``idx_b`` for gather_mm), one ``torch.matmul`` per segment,
                                            scattered back
+(none: the reference has no attention)     :func:`attention` / :func:`attention_backward`: gather, per-entry dot,
+                                           :func:`segment_softmax` per head, ``index_add``
 =========================================  ====================================================================
 """
 
@@ -184,6 +186,52 @@ def segment_softmax_backward(ptr: torch.Tensor, perm, y: torch.Tensor, g: torch.
     a, b = (gg, yy.exp()) if log_form else (gg * yy, yy)
     total = torch.zeros(n_groups, dtype=acc).index_add(0, grp, a)
     return _from_plan_order(a - b * total[grp], perm, y.dtype)
+
+
+def _attention_terms(ptr, idx, perm, bias, Q, K, heads: int, scale: float):
+    """(row of every entry, its column, the logits [nnz, heads]) of the walk (ptr, idx, perm) in the accumulator type."""
+    acc = torch.float32 if Q.dtype == torch.bfloat16 else Q.dtype
+    n, nnz = ptr.numel() - 1, idx.numel()
+    rows, cols = _segment_ids(ptr, n, nnz), idx.reshape(-1).to(torch.int64)
+    q, k = Q.to(acc).view(Q.size(0), heads, -1), K.to(acc).view(K.size(0), heads, -1)
+    t = (q.index_select(0, rows) * k.index_select(0, cols)).sum(-1) * scale
+    if bias is not None:
+        b = bias.reshape(-1) if perm is None else bias.reshape(-1).index_select(0, perm.to(torch.int64))
+        t = t + b.to(acc).unsqueeze(1)
+    return rows, cols, t
+
+
+def attention(ptr, idx, perm, bias, Q, K, V, heads: int, scale: float):
+    """(O [n, heads·d], P [nnz, heads]) of attention over the pattern walked by rows as (ptr, idx, perm): gather, per-entry dot,
+    the segmented softmax of every head over the rows' entries, index_add.  A row without entries gives zeros; a row whose logits
+    hold a NaN or +inf, or nothing but -inf, is NaN (as :func:`segment_softmax`).  bf16 is computed in fp32 and rounded once."""
+    _cpu_only(ptr, idx, perm, bias, Q, K, V)
+    n = ptr.numel() - 1
+    rows, cols, t = _attention_terms(ptr, idx, perm, bias, Q, K, heads, scale)
+    P = torch.stack([segment_softmax(ptr, None, t[:, h].contiguous(), n, False) for h in range(heads)], 1)
+    v = V.to(P.dtype).view(V.size(0), heads, -1)
+    O = torch.zeros((n, heads, v.size(-1)), dtype=P.dtype).index_add_(0, rows, P.unsqueeze(-1) * v.index_select(0, cols))
+    return O.view(n, -1).to(Q.dtype), P
+
+
+def attention_backward(ptr, idx, perm, Q, K, V, dO, P, heads: int, scale: float, want_dA: bool):
+    """(dQ, dK, dV, dA or None) of :func:`attention` from its probabilities P: dP = <dO[i], V[j]>, δ[i] = Σ_j P·dP,
+    dS = P·(dP − δ); dQ = scale·Σ_j dS·K[j], dK = scale·Σ_i dS·Q[i], dV = Σ_i P·dO[i], dA = Σ_heads dS at the entry's own
+    position of the value array."""
+    _cpu_only(ptr, idx, perm, Q, K, V, dO, P)
+    acc = P.dtype
+    n, m, nnz = Q.size(0), K.size(0), idx.numel()
+    rows, cols = _segment_ids(ptr, n, nnz), idx.reshape(-1).to(torch.int64)
+    q, k, v, g = (x.to(acc).view(x.size(0), heads, -1) for x in (Q, K, V, dO))
+    gi = g.index_select(0, rows)
+    dP = (gi * v.index_select(0, cols)).sum(-1)
+    delta = torch.zeros((n, heads), dtype=acc).index_add_(0, rows, P * dP)
+    dS = P * (dP - delta.index_select(0, rows))
+    dQ = torch.zeros_like(q).index_add_(0, rows, dS.unsqueeze(-1) * k.index_select(0, cols)) * scale
+    dK = torch.zeros_like(k).index_add_(0, cols, dS.unsqueeze(-1) * q.index_select(0, rows)) * scale
+    dV = torch.zeros_like(v).index_add_(0, cols, P.unsqueeze(-1) * gi)
+    dA = _from_plan_order(dS.sum(1), perm, acc) if want_dA else None
+    return dQ.view(n, -1).to(Q.dtype), dK.view(m, -1).to(Q.dtype), dV.view(m, -1).to(Q.dtype), dA
 
 
 def segment_mm(bounds, perm, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
