@@ -623,6 +623,10 @@ int tsgu_cg_update2(int vtype, int64_t n, int64_t p, const void* r, void* pvec,
  *                          | 2 three dot partials (a0=t,a1=s,a2=r0) | 3 x/r update (a0=x,a1=r,a2=s,a3=t,a4=p)
  * Vector operands are contiguous [n][p], 16-byte aligned; partial buffers have tsgu_cg_num_blocks() rows per set.
  * Every step is a no-op once flags[0] != 0.
+ * Widths as for K7 below.  The library's own driver (utils/bicgstab.py) calls these entries with at most 256 columns: wider
+ * right-hand sides are solved 256 columns at a time, since the columns are independent problems and a column's sums (hence its
+ * iterates, in their last bits) depend on the width of the array it sits in.  The instances above 256 columns are kept for
+ * callers of the C ABI and are covered by the step tests only.
  */
 int tsgu_bicg_scalar(int vtype, int phase, const void* partial, int64_t n_partial, int64_t set_stride, void* fold,
                      void* scal, int* flags, double abstol, double reltol, int matvec_max, int nmv0, int64_t p,
@@ -649,7 +653,10 @@ int tsgu_bicg_update_x_precond(int vtype, int64_t n, int64_t p, void* x, void* r
  * 9 diag | 10 scale of this update | 11 beta of the previous step; flags: int32 [0] stop, [1] iterations.  The caller
  * initialises rows 1, 6, 11 with the initial beta and rows 2, 4 with ones.  Arrays are contiguous [n][p], 16-byte
  * aligned; partial sets are `set_stride` elements apart with tsgu_cg_num_blocks(vtype, n, p) rows each; `fold`
- * (tsgu_cg_fold_rows() x p) is scratch for long partial lists.  fp32 / fp64, p <= 1024.
+ * (tsgu_cg_fold_rows() x p) is scratch for long partial lists.  fp32 / fp64.  Widths (the same for the K5 and K6 vector
+ * steps): any p <= 256; above that p must be a multiple of the 16-byte lane width (4 fp32 / 2 fp64 columns) and at most 256
+ * lanes wide, i.e. p <= 1024 in fp32 and p <= 512 in fp64.  Other widths return TSGU_ERR_TOO_LARGE and
+ * tsgu_cg_num_blocks() returns -1 for them.
  */
 int tsgu_minres_scalar(int vtype, int phase, const void* partial, int64_t n_partial, int64_t set_stride, void* fold,
                        void* scal, int* flags, double eps, double tol, double shift, int64_t p, int device, void* stream);

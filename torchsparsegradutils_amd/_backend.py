@@ -1099,8 +1099,28 @@ def index_fingerprint_match(tensors, refs=None, copy: bool = False, hash: bool =
     return out, copies
 
 
+KRYLOV_SLAB = 256      # columns one workgroup of the Krylov kernels covers with scalar lanes (kBlock in csrc/tsgu_common.h)
+
+
+def krylov_width_rule(dtype: torch.dtype) -> str:
+    """The column counts the fused step kernels (K5, K6, K7 of include/tsgu_hip.h) accept, in words."""
+    wide = 16 // torch.empty((), dtype=dtype).element_size()
+    return (f"any number up to {KRYLOV_SLAB}, and above that multiples of {wide} up to {KRYLOV_SLAB * wide} "
+            f"(16-byte lanes of {wide} {dtype} columns)")
+
+
+def krylov_num_blocks(who: str, t: torch.Tensor, n: int, p: int) -> int:
+    """tsgu_cg_num_blocks for an (n, p) state of t's dtype; a width the step kernels do not take raises with the rule."""
+    nb = load_library().tsgu_cg_num_blocks(vtype_of(t), n, p)
+    if nb < 0:
+        raise RuntimeError(f"{who}: {p} simultaneous right-hand sides are not supported by the fused kernels, which take "
+                           f"{krylov_width_rule(t.dtype)}")
+    return nb
+
+
 def coldot(X, Y):
-    """Column-wise dot products of two (n, p) arrays -> (p,) tensor (deterministic)."""
+    """Column-wise dot products of two (n, p) arrays -> (p,) tensor (deterministic).  More than 256 columns are walked in
+    slabs of 256 through the operands' leading dimensions (tsgu_coldot reads strided rows), one launch pair per slab."""
     if not X.is_cuda and not Y.is_cuda:
         from . import _cpu
 
@@ -1111,12 +1131,14 @@ def coldot(X, Y):
         raise RuntimeError(f"tsgu_coldot: expected both operands to have the same dtype, got {X.dtype} and {Y.dtype}")
     X, Y = rowmajor(X), rowmajor(Y)
     n, p = X.shape
-    nb = lib.tsgu_coldot_max_blocks(n, p)
-    if nb < 0:
-        raise RuntimeError("tsgu_coldot: more than 256 right-hand sides are not supported by the fused path")
-    partial = torch.empty((nb, p), dtype=X.dtype, device=dev)
+    vt, ldx, ldy = vtype_of(X), _ld(X), _ld(Y)
     out = torch.empty((p,), dtype=X.dtype, device=dev)
-    launch("tsgu_coldot", dev, vtype_of(X), n, p, X, _ld(X), Y, _ld(Y), partial, out)
+    if p == 0:
+        return out
+    partial = torch.empty((lib.tsgu_coldot_max_blocks(n, min(p, KRYLOV_SLAB)), min(p, KRYLOV_SLAB)), dtype=X.dtype, device=dev)
+    for c0 in range(0, p, KRYLOV_SLAB):
+        w = min(KRYLOV_SLAB, p - c0)
+        launch("tsgu_coldot", dev, vt, n, w, X[:, c0:], ldx, Y[:, c0:], ldy, partial, out[c0:])
     return out
 
 

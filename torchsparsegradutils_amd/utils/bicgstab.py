@@ -57,6 +57,15 @@ def bicgstab(
         raise RuntimeError("settings.precon must be a tensor, or a callable object!")
     if ENABLE_FUSED and rhs.is_cuda and rhs.dtype in (torch.float32, torch.float64) and rhs.dim() in (1, 2) \
             and rhs.shape[-1 if rhs.dim() == 2 else 0] > 0 and (rhs.dim() == 1 or rhs.shape[1] <= 1024):
+        if rhs.dim() == 2 and rhs.shape[1] > _be.KRYLOV_SLAB:
+            # The columns are independent problems (the reference solves them one after the other), so more than 256 of them are
+            # solved 256 at a time: a column's solution then depends on no column outside its slab — the leading 256 columns of a
+            # wider solve are, bit for bit, the solve of those columns alone (the column sums of a wider array would be associated
+            # differently).  The widths are those the step kernels accept, as for linear_cg and minres.
+            _be.krylov_num_blocks("bicgstab", rhs, rhs.shape[0], rhs.shape[1])
+            slabs = [slice(c, min(c + _be.KRYLOV_SLAB, rhs.shape[1])) for c in range(0, rhs.shape[1], _be.KRYLOV_SLAB)]
+            return torch.cat([_bicgstab_fused(matmul_closure, rhs[:, c].contiguous(),
+                                              None if initial_guess is None else initial_guess[:, c], settings) for c in slabs], dim=1)
         return _bicgstab_fused(matmul_closure, rhs, initial_guess, settings)
     if rhs.dim() > 1:
         # column-by-column, exactly like the reference (each column has its own stopping point)
@@ -169,9 +178,7 @@ def _bicgstab_fused(matmul_closure, rhs, initial_guess, settings: BICGSTABSettin
         r0 = B.clone()  # the reference does not subtract A·x0 (bicgstab.py:158)
         nmv0 = 0
 
-    nb = lib.tsgu_cg_num_blocks(vt, n, p)
-    if nb < 0:
-        raise RuntimeError("bicgstab: more than 1024 simultaneous right-hand sides are not supported")
+    nb = _be.krylov_num_blocks("bicgstab", B, n, p)
     scal = torch.zeros(8 * p, dtype=dtype, device=dev)
     flags = torch.zeros(2 + 3 * p, dtype=torch.int32, device=dev)
     part = torch.empty((3, nb, p), dtype=dtype, device=dev)

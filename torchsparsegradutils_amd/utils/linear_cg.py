@@ -114,7 +114,7 @@ def linear_cg(
     rhs = rhs.div(rhs_norm)
 
     if x0 is None:
-        result = torch.zeros_like(rhs)
+        result = torch.zeros_like(rhs, memory_format=torch.contiguous_format)   # (the kernels take contiguous [n][p] arrays whatever rhs is)
         residual = rhs - checked(op(result), rhs.dtype)  # reference :266 (kept: it is also the NaN probe of :278)
     else:
         result = x0.div(rhs_norm).expand_as(rhs).contiguous()
@@ -371,9 +371,7 @@ def _fused_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, toleranc
     n, p = r.shape
     dev, dtype = r.device, r.dtype
     vt = _be.vtype_of(r)
-    nb_upd = lib.tsgu_cg_num_blocks(vt, n, p)
-    if nb_upd < 0:
-        raise RuntimeError("linear_cg: more than 1024 simultaneous right-hand sides are not supported")
+    nb_upd = _be.krylov_num_blocks("linear_cg", r, n, p)
 
     fused_dot = isinstance(op, SparseOperator) and op.dtype == dtype
 

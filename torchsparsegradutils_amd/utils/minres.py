@@ -184,9 +184,7 @@ def _minres_fused(op, rhs: torch.Tensor, shifts: torch.Tensor, value, precond, e
     vt = _be.vtype_of(rhs)
     fused_dot = isinstance(op, SparseOperator) and op.dtype == dtype
     val = 1.0 if value is None else float(value)
-    nb = lib.tsgu_cg_num_blocks(vt, n, p)
-    if nb < 0:
-        raise RuntimeError("minres: more than 1024 simultaneous right-hand sides are not supported")
+    nb = _be.krylov_num_blocks("minres", rhs, n, p)
 
     z = [torch.zeros_like(rhs), rhs.clone()]                     # [z two steps back, z one step back]
     if precond is None:
