@@ -2,7 +2,7 @@
 
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
-and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` beside them;
+and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -14,6 +14,7 @@ from .sparse_attention import SparseAttention, sparse_attention
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
+from .sparse_mm_reduce import SparseMMReduce, sparse_mm_reduce
 from .sparse_softmax import SparseSoftmax, sparse_log_softmax, sparse_softmax
 from .sparse_solve import (
     SparseGenericSolve,
@@ -24,6 +25,7 @@ from .sparse_solve import (
 
 __all__ = [
     "sparse_mm",
+    "sparse_mm_reduce",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",
@@ -38,6 +40,7 @@ __all__ = [
     "wait_for_plans",
     "poll_errors",
     "SparseMatMul",
+    "SparseMMReduce",
     "SparseTriangularSolve",
     "SparseGenericSolve",
     "SparseLogSumExp",

@@ -177,6 +177,17 @@ SIGNATURES_ATTENTION = {
                _int, _dbl, _ptr, _i64, _ptr, _i64, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_mm_reduce.h (same library, same ABI version)
+SIGNATURES_MM_REDUCE = {
+    "tsgu_csr_spmm_reduce_geometry": (_int, [_int, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_spmm_reduce": (
+        _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _ptr, _i64, _ptr, _i64, _int, _ptr]),
+    "tsgu_csr_spmm_reduce_backward_values": (
+        _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _ptr, _int, _ptr]),
+    "tsgu_csr_spmm_reduce_backward_dense": (
+        _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -199,7 +210,8 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
+                                  *SIGNATURES_MM_REDUCE.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -884,6 +896,67 @@ def csr_attention_backward(walk, twalk, bias, Q, K, V, dO, lse, heads: int, d: i
     launch("tsgu_csr_attention_backward_cols", dev, vt, it, n, m, nnz, tptr, tidx, tperm, bias, Q, _ld(Q), K, _ld(K), V,
            _ld(V), dO, _ld(dO), lse, delta, heads, d, float(scale), dK, _ld(dK), dV, _ld(dV))
     return dQ, dK, dV, dA
+
+
+MM_REDUCE_OPS = {"amax": 0, "amin": 1}
+
+
+def spmm_reduce_geometry(dtype: torch.dtype, p: int):
+    """(rows per workgroup, entries of one staging pass, columns per grid.z slice) of the max / min product kernels for `p` columns
+    of value type `dtype` with 16-byte aligned operands: the sizes at which their walk changes path.  Host only."""
+    rpb, stage, width = _int(0), _int(0), _int(0)
+    check(load_library().tsgu_csr_spmm_reduce_geometry(_VTYPE[dtype], int(p), ctypes.byref(rpb), ctypes.byref(stage),
+                                                       ctypes.byref(width)), "tsgu_csr_spmm_reduce_geometry")
+    return int(rpb.value), int(stage.value), int(width.value)
+
+
+def _reduce_operands(index_arrays, val, *dense):
+    dev = require_device(*index_arrays, val, *dense)
+    first = index_arrays[0]
+    for t in index_arrays:
+        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
+            raise RuntimeError("the index arrays of a max / min product must be contiguous 1-D arrays of one dtype")
+    ref = dense[0]
+    for t in dense:
+        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1) or (t.stride(1) != 1 and t.size(1) > 1) or (
+                t.size(0) > 1 and t.stride(0) < t.size(1)):
+            raise RuntimeError("the dense operands of a max / min product must be 2-D row-major arrays of one dtype and width")
+    if val is not None and (val.dtype != ref.dtype or val.dim() != 1 or not val.is_contiguous()):
+        raise RuntimeError(f"expected A and B to have the same dtype, got {val.dtype} and {ref.dtype}")
+    return dev
+
+
+def csr_spmm_reduce(crow, col, val, B, n_rows: int, n_cols: int, reduce: str):
+    """(C [n_rows, p], arg [n_rows, p] int32) of the max / min product of the 2-D CSR arrays with B [n_cols, p]: arg is the
+    winning entry's position in `val` (−1 for a row without entries)."""
+    dev = _reduce_operands((crow, col), val, B)
+    p = B.size(1)
+    if p < 1:
+        raise RuntimeError("the max / min product needs at least one column")
+    C = torch.empty((n_rows, p), dtype=B.dtype, device=dev)
+    arg = torch.empty((n_rows, p), dtype=torch.int32, device=dev)
+    launch("tsgu_csr_spmm_reduce", dev, vtype_of(B), itype_of(crow), n_rows, n_cols, col.numel(), crow, col, val, B, _ld(B), p,
+           MM_REDUCE_OPS[reduce], C, p, arg, p)
+    return C, arg
+
+
+def csr_spmm_reduce_backward_values(crow, col, arg, G, B, n_rows: int, n_cols: int):
+    """dval[e] = Σ_{k: arg[i,k] = e} G[i,k]·B[col[e],k], in the order of the value array."""
+    dev = _reduce_operands((crow, col), None, G, B)
+    dval = torch.empty((col.numel(),), dtype=B.dtype, device=dev)
+    launch("tsgu_csr_spmm_reduce_backward_values", dev, vtype_of(B), itype_of(crow), n_rows, n_cols, col.numel(), crow, col, arg,
+           _ld(arg), G, _ld(G), B, _ld(B), G.size(1), dval)
+    return dval
+
+
+def csr_spmm_reduce_backward_dense(tptr, tidx, perm, val, arg, G, n_rows: int, n_cols: int):
+    """dB[j,k] = Σ_{e in column j: arg[i,k] = e} val[e]·G[i,k] over the transposed walk (tptr, tidx, perm into val)."""
+    dev = _reduce_operands((tptr, tidx, perm), val, G)
+    p = G.size(1)
+    dB = torch.empty((n_cols, p), dtype=G.dtype, device=dev)
+    launch("tsgu_csr_spmm_reduce_backward_dense", dev, vtype_of(G), itype_of(tptr), n_rows, n_cols, tidx.numel(), tptr, tidx, perm,
+           val, arg, _ld(arg), G, _ld(G), p, dB, p)
+    return dB
 
 
 SEGMENT_MM_TILE_ROWS = 128       # kImmBM of csrc/indexed_mm_impl.h: the row tile of the plans' tile prefix

@@ -22,6 +22,7 @@ nested-tensor ``segment_mm`` / ``gather_mm``        :func:`segment_mm` / :func:`
                                            scattered back
 (none: the reference has no attention)     :func:`attention` / :func:`attention_backward`: gather, per-entry dot,
                                            :func:`segment_softmax` per head, ``index_add``
+``torch.sparse.mm(A, B, reduce)`` (ATen)   :func:`mm_reduce` / :func:`mm_reduce_backward` on the 2-D CSR arrays
 =========================================  ====================================================================
 """
 
@@ -358,3 +359,30 @@ def csr_row_sumsq_backward(plan: _pt.RowGather, values: torch.Tensor, w, g: torc
     out = torch.empty_like(q)
     out[plan.perm.reshape(-1).to(torch.int64)] = q
     return out
+
+
+def mm_reduce(crow: torch.Tensor, col: torch.Tensor, values: torch.Tensor, B: torch.Tensor, shape, reduce: str) -> torch.Tensor:
+    """``torch.sparse.mm(A, B, reduce)`` for the 2-D CSR arrays of A (block diagonal for a batched operand: absent entries do not
+    take part, so the items do not see each other) — the CPU op whose semantics the HIP kernels of csrc/mm_reduce.hip restate."""
+    _cpu_only(crow, col, values, B)
+    # With an operand that requires a gradient the op runs the loop that tracks the winners — strict compare, the first of equal
+    # candidates stays — and without one a vectorised maximum, which picks another sign for a tie of +0.0 and -0.0: the tracking
+    # loop always, so that the result does not depend on who asks for gradients.
+    with torch.enable_grad():
+        A = torch.sparse_csr_tensor(crow, col, values.detach(), shape).requires_grad_(True)
+        return torch.sparse.mm(A, B.detach(), reduce).detach()
+
+
+def mm_reduce_backward(crow, col, values, B, shape, reduce: str, G, need_a: bool, need_b: bool):
+    """(gradient of the values or None, gradient of B or None) of :func:`mm_reduce` by the op's own backward: the forward is
+    evaluated again (the op keeps its winners to itself)."""
+    _cpu_only(crow, col, values, B, G)
+    with torch.enable_grad():
+        A = torch.sparse_csr_tensor(crow, col, values.detach(), shape).requires_grad_(need_a)
+        Bg = B.detach().requires_grad_(need_b)
+        C = torch.sparse.mm(A, Bg, reduce)
+        wanted = [t for t, need in ((A, need_a), (Bg, need_b)) if need]
+        grads = list(torch.autograd.grad(C, wanted, G))
+    ga = grads.pop(0).values() if need_a else None
+    gb = grads.pop(0) if need_b else None
+    return ga, gb
