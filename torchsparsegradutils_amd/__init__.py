@@ -2,7 +2,7 @@
 
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
-and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` beside them;
+and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -16,6 +16,7 @@ from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
 from .sparse_mm_reduce import SparseMMReduce, sparse_mm_reduce
 from .sparse_softmax import SparseSoftmax, sparse_log_softmax, sparse_softmax
+from .sparse_spgemm import SparseSpGEMM, sparse_spgemm
 from .sparse_solve import (
     SparseGenericSolve,
     SparseTriangularSolve,
@@ -26,6 +27,7 @@ from .sparse_solve import (
 __all__ = [
     "sparse_mm",
     "sparse_mm_reduce",
+    "sparse_spgemm",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",
@@ -41,6 +43,7 @@ __all__ = [
     "poll_errors",
     "SparseMatMul",
     "SparseMMReduce",
+    "SparseSpGEMM",
     "SparseTriangularSolve",
     "SparseGenericSolve",
     "SparseLogSumExp",

@@ -188,6 +188,20 @@ SIGNATURES_MM_REDUCE = {
         _int, [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_spgemm.h (same library, same ABI version)
+SIGNATURES_SPGEMM = {
+    "tsgu_spgemm_bins": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_spgemm_row_bound": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_spgemm_symbolic": (
+        _int, [_int, _int, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_spgemm_numeric": (
+        _int, [_int, _int, _int, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_spgemm_grad_a": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_spgemm_grad_b": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -211,7 +225,7 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
-                                  *SIGNATURES_MM_REDUCE.items()):
+                                  *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -959,7 +973,106 @@ def csr_spmm_reduce_backward_dense(tptr, tidx, perm, val, arg, G, n_rows: int, n
     return dB
 
 
-SEGMENT_MM_TILE_ROWS = 128       # kImmBM of csrc/indexed_mm_impl.h: the row tile of the plans' tile prefix
+# kSpgemmLimit / kSpgemmGroup of csrc/spgemm_impl.h (tsgu_spgemm_bins reports them): the sparse × sparse kernels bin the rows of C by
+# a per-row measure x — the upper bound Σ_k nnz(B[k,:]) in the symbolic phase, the row's length in the numeric one.  Bin b holds
+# SPGEMM_BIN_LIMITS[b-1] < x <= SPGEMM_BIN_LIMITS[b] and keeps a row in LDS with SPGEMM_BIN_LANES[b] lanes; rows above the last
+# limit work in global memory, one workgroup each.
+SPGEMM_BIN_LIMITS = (32, 512, 4096)
+SPGEMM_BIN_LANES = (8, 64, 256, 256)
+SPGEMM_SCRATCH_MIN = 8192        # smallest sort buffer of the global bin: the power of two above the last limit
+
+
+def spgemm_bins():
+    """(limits, lanes per row) as the library reports them.  Host only."""
+    limits, lanes = (_int * 3)(), (_int * 4)()
+    check(load_library().tsgu_spgemm_bins(limits, lanes), "tsgu_spgemm_bins")
+    return tuple(limits), tuple(lanes)
+
+
+def _spgemm_indices(*arrays):
+    first = arrays[0]
+    for t in arrays:
+        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
+            raise RuntimeError("the index arrays of a sparse × sparse product must be contiguous 1-D arrays of one dtype")
+    return itype_of(first)
+
+
+def _spgemm_values(*arrays):
+    first = arrays[0]
+    for t in arrays:
+        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
+            raise RuntimeError("the value arrays of a sparse × sparse product must be contiguous 1-D arrays of one dtype")
+    return vtype_of(first)
+
+
+def spgemm_row_bound(a_crow, a_col, b_crow, n_rows: int, n_inner: int):
+    """ub[i] = Σ_{k ∈ A[i,:]} nnz(B[k,:]) as int64."""
+    dev = require_device(a_crow, a_col, b_crow)
+    it = _spgemm_indices(a_crow, a_col, b_crow)
+    ub = torch.zeros(n_rows, dtype=torch.int64, device=dev)
+    launch("tsgu_spgemm_row_bound", dev, it, n_rows, n_inner, a_crow, a_col, b_crow, ub)
+    return ub
+
+
+def spgemm_symbolic(bin: int, rows, dims, a_crow, a_col, b_crow, b_col, scratch=None, sptr=None, cnt=None, c_crow=None, c_col=None):
+    """One bin of the symbolic phase over the int32 row list `rows`: counts into `cnt` (int64, per row), or — with `c_crow` and
+    `c_col` — writes the rows' ascending columns.  `scratch` / `sptr`: the sort buffers of the global bin."""
+    dev = require_device(rows, a_crow, a_col, b_crow, b_col, scratch, sptr, cnt, c_crow, c_col)
+    fill = c_col is not None
+    it = _spgemm_indices(a_crow, a_col, b_crow, b_col, *((c_crow, c_col) if fill else ()))
+    if rows.dtype != torch.int32 or not rows.is_contiguous() or (cnt is not None and cnt.dtype != torch.int64):
+        raise RuntimeError("sparse × sparse product: row lists are contiguous int32 arrays, counts int64")
+    if bin == len(SPGEMM_BIN_LIMITS) and (scratch is None or scratch.dtype != torch.int32 or sptr is None or sptr.dtype != torch.int64
+                                          or sptr.numel() != rows.numel() + 1):
+        raise RuntimeError("sparse × sparse product: the global bin sorts int32 scratch slices addressed by an int64 pointer array")
+    n, k, m = dims
+    launch("tsgu_spgemm_symbolic", dev, it, bin, rows.numel(), rows, n, k, m, a_crow, a_col, b_crow, b_col, scratch, sptr,
+           int(fill), cnt, c_crow, c_col)
+
+
+def spgemm_numeric(bin: int, rows, dims, a_crow, a_col, a_val, b_crow, b_col, b_val, c_crow, c_col, c_val, acc=None):
+    """One bin of the numeric phase over the int32 row list `rows`: the rows' values go to `c_val`."""
+    dev = require_device(rows, a_crow, a_col, a_val, b_crow, b_col, b_val, c_crow, c_col, c_val, acc)
+    it = _spgemm_indices(a_crow, a_col, b_crow, b_col, c_crow, c_col)
+    vt = _spgemm_values(a_val, b_val, c_val)
+    if rows.dtype != torch.int32 or not rows.is_contiguous():
+        raise RuntimeError("sparse × sparse product: row lists are contiguous int32 arrays")
+    if c_col.numel() != c_val.numel() or a_col.numel() != a_val.numel() or b_col.numel() != b_val.numel():
+        raise RuntimeError("sparse × sparse product: one value per stored entry")
+    if bin == len(SPGEMM_BIN_LIMITS) and (acc is None or acc.dtype != _acc_dtype(c_val.dtype) or acc.numel() < c_val.numel()):
+        raise RuntimeError("sparse × sparse product: the global bin accumulates in nnz(C) entries of the accumulator type")
+    n, k, m = dims
+    launch("tsgu_spgemm_numeric", dev, vt, it, bin, rows.numel(), rows, n, k, m, a_crow, a_col, a_val, b_crow, b_col, b_val, c_crow,
+           c_col, acc, c_val)
+
+
+def spgemm_grad_a(dims, a_row, a_col, b_crow, b_col, b_val, c_crow, c_col, g):
+    """gradA at A's stored positions: Σ_{t ∈ B[k,:]} g[pos_C(i, col_t)]·b_t, in B's stored order."""
+    dev = require_device(a_row, a_col, b_crow, b_col, b_val, c_crow, c_col, g)
+    it = _spgemm_indices(a_row, a_col, b_crow, b_col, c_crow, c_col)
+    vt = _spgemm_values(b_val, g)
+    if g.numel() != c_col.numel() or b_val.numel() != b_col.numel() or a_row.numel() != a_col.numel():
+        raise RuntimeError("sparse × sparse product: one value per stored entry")
+    out = torch.empty(a_col.numel(), dtype=b_val.dtype, device=dev)
+    n, k, m = dims
+    launch("tsgu_spgemm_grad_a", dev, vt, it, n, k, m, a_col.numel(), a_row, a_col, b_crow, b_col, b_val, c_crow, c_col, g, out)
+    return out
+
+
+def spgemm_grad_b(dims, b_row, b_col, t_crow, t_idx, t_perm, a_val, c_crow, c_col, g):
+    """gradB at B's stored positions: Σ_{i ∈ column k of A} a_ik·g[pos_C(i, j)], in the order of A's transposed pattern."""
+    dev = require_device(b_row, b_col, t_crow, t_idx, t_perm, a_val, c_crow, c_col, g)
+    it = _spgemm_indices(b_row, b_col, t_crow, t_idx, t_perm, c_crow, c_col)
+    vt = _spgemm_values(a_val, g)
+    if g.numel() != c_col.numel() or a_val.numel() != t_idx.numel() or t_perm.numel() != t_idx.numel() or b_row.numel() != b_col.numel():
+        raise RuntimeError("sparse × sparse product: one value per stored entry")
+    out = torch.empty(b_col.numel(), dtype=a_val.dtype, device=dev)
+    n, k, m = dims
+    launch("tsgu_spgemm_grad_b", dev, vt, it, n, k, m, b_col.numel(), b_row, b_col, t_crow, t_idx, t_perm, a_val, c_crow, c_col, g, out)
+    return out
+
+
+SEGMENT_MM_TILE_ROWS = 128      # kImmBM of csrc/indexed_mm_impl.h: the row tile of the plans' tile prefix
 
 
 def segment_mm_grad_b_workspace(dtype: torch.dtype, n: int, n_seg: int, d1: int, d2: int):

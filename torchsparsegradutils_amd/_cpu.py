@@ -23,6 +23,7 @@ nested-tensor ``segment_mm`` / ``gather_mm``        :func:`segment_mm` / :func:`
 (none: the reference has no attention)     :func:`attention` / :func:`attention_backward`: gather, per-entry dot,
                                            :func:`segment_softmax` per head, ``index_add``
 ``torch.sparse.mm(A, B, reduce)`` (ATen)   :func:`mm_reduce` / :func:`mm_reduce_backward` on the 2-D CSR arrays
+``torch.sparse.mm(S1, S2)`` (ATen)         :func:`spgemm` / :func:`spgemm_backward` on coalesced COO operands
 =========================================  ====================================================================
 """
 
@@ -386,3 +387,30 @@ def mm_reduce_backward(crow, col, values, B, shape, reduce: str, G, need_a: bool
     ga = grads.pop(0).values() if need_a else None
     gb = grads.pop(0) if need_b else None
     return ga, gb
+
+
+def spgemm(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """``torch.sparse.mm(A, B)`` of two coalesced COO operands (float32 or float64): the structural product, coalesced."""
+    _cpu_only(A, B)
+    return torch.sparse.mm(A, B).coalesce()
+
+
+def spgemm_backward(A: torch.Tensor, B: torch.Tensor, G: torch.Tensor, need_a: bool, need_b: bool):
+    """(values of dL/dA, values of dL/dB) of :func:`spgemm` for the sparse gradient ``G`` on the product's pattern: torch's own
+    backward of the op, which masks either gradient by its operand's pattern; values in the operand's (coalesced) order."""
+    _cpu_only(A, B, G)
+    with torch.enable_grad():
+        a, b = A.detach().requires_grad_(need_a), B.detach().requires_grad_(need_b)
+        C = torch.sparse.mm(a, b)
+    wanted = [t for t, need in ((a, need_a), (b, need_b)) if need]
+    grads = list(torch.autograd.grad(C, wanted, G)) if wanted else []
+    out = []
+    for t, need in ((A, need_a), (B, need_b)):
+        if not need:
+            out.append(None)
+            continue
+        g = grads.pop(0).coalesce()
+        if g._nnz() != t._nnz() or not torch.equal(g._indices(), t._indices()):
+            raise RuntimeError("torch.sparse.mm returned a gradient that is not on its operand's pattern")
+        out.append(g._values())
+    return out[0], out[1]
