@@ -1,14 +1,19 @@
-// Segmented log-sum-exp over a row-gather pattern and its gradient (sparse_logsumexp / sparse_bidir_logsumexp).
+// Segmented reductions over a row-gather pattern: the range walk that sparse_logsumexp / sparse_bidir_logsumexp and sparse_softmax /
+// sparse_log_softmax (softmax_impl.h) share, and the log-sum-exp kernels themselves.
 //
-// Forward.  The entries are cut into contiguous ranges of kLseRange entries, one wave each (balanced by entries, not by
-// groups: one group of 2^20 entries among short ones occupies 2^20 / kLseRange waves).  A wave loads its range with 16-byte
-// loads (or through `perm`, for the column direction) into LDS, then reduces every group it owns — the groups whose first
-// entry lies in the range — lane per group for short ones and the whole wave for long ones.  A group that runs past the range
-// leaves a (max, sum) partial in the wave's tail slot, and every later wave it reaches leaves one in its head slot; a second
-// kernel merges those partials in a fixed order.  No float atomics: the same inputs give the same bits, and a direction
-// computed alone or as half of the bidirectional call is the same kernel with the same operands.
+// The walk.  The entries are cut into contiguous ranges of lse_range<Acc>() entries, one wave each (balanced by entries, not by
+// groups: one group of 2^20 entries among short ones occupies 2^20 / range waves).  A wave stages its range in LDS as accumulator
+// values (seg_stage: 16-byte loads, or through `perm` for the column direction), then seg_walk reduces every group it owns — the
+// groups whose first entry lies in the range — lane per group for short ones and the whole wave for long ones.  A group that runs
+// past the range leaves a partial in the wave's tail slot, and every later wave it reaches leaves one in its head slot;
+// seg_merge_kernel merges those partials in a fixed order, and for operators with one value per entry seg_fix_kernel rewrites the
+// entries of the crossing pieces.  No float atomics: the same inputs give the same bits.  What is reduced and what happens to a
+// finished group comes from an operation object (MaxSumExp, LseOp here; SmFwdOp, SmBwdOp in softmax_impl.h).
 //
-// Backward.  One streaming pass in the stored order: each entry finds its primary group from `ptr` (a search in the wave's
+// Log-sum-exp forward.  The (max, Σ exp) partial; a finished group is one value, written by one lane.  A direction computed alone
+// or as half of the bidirectional call is the same kernel with the same operands.
+//
+// Log-sum-exp backward.  One streaming pass in the stored order: each entry finds its primary group from `ptr` (a search in the wave's
 // window of ptr, staged in LDS), reads the secondary index only when that direction is present, and gathers g / lse of the
 // groups it belongs to.
 #pragma once
@@ -24,6 +29,9 @@ constexpr int lse_range() { return kLseStageBytes / (int)sizeof(Acc); }
 // owned groups up to this many entries are reduced by one lane each; longer ones by the whole wave
 constexpr int kLseLaneMax = 48;
 constexpr int kLseWavesPerBlock = kBlock / kWave;
+// workspace words of one range: the head partial from word 0, the tail partial (after the merge: the group's result) from kSegTail
+constexpr int kSegSlots = 4;
+constexpr int kSegTail = 2;
 
 // max that propagates NaN (a NaN value makes its group NaN)
 template <typename Acc>
@@ -88,13 +96,211 @@ __device__ __forceinline__ int64_t wave_lower_bound(const I* __restrict__ p, int
     return hi;
 }
 
+// ---- the walk ------------------------------------------------------------------------------------------------------------
+// An operation object `Op` supplies what differs between the operators:
+//   Op::Acc, Op::Part, Op::Params      accumulator type, partial of a piece, the kernels' parameter block
+//   identity(), combine(a, b), wave_combine(p), put(slot, p), get(slot)      partials: merging them, and their workspace form
+//   lane_reduce(st, lo, hi), wave_reduce(st, lo, hi, lane)                   st[lo, hi) by one lane / by the whole wave (every lane: p)
+//   lane_finish(st, lo, hi, g, count, p), wave_finish(..., p, lane)          group g of `count` entries ends in the range
+// and, as static functions of the parameter block (the merge and fix-up kernels walk nothing and build no object):
+//   merged_finish(P, slot, g, count, p)                                      a crossing group's merged partial, at its owner's tail slot
+//   merged(slot), fix(P, at, t)                                              (one value per entry) entry `at` of a crossing group
+
+// entries of range w
+template <typename Acc>
+__device__ __forceinline__ int seg_len(int64_t w, int64_t nnz) {
+    constexpr int R = lse_range<Acc>();
+    const int64_t s = w * R;
+    return (int)((s + R < nnz ? s + R : nnz) - s);
+}
+
+// The wave's `len` entries from `s` of `src` (through perm when given) into LDS as accumulator values, f applied to each.
+template <typename V, typename I, typename F>
+__device__ __forceinline__ void seg_stage(typename VT<V>::Acc* st, const V* __restrict__ src, const I* __restrict__ perm, int64_t s,
+                                          int len, bool vec, int lane, F f) {
+    using Acc = typename VT<V>::Acc;
+    constexpr int W = VT<V>::kWide;
+    if (perm == nullptr && vec) {
+        for (int i = lane * W; i < len; i += kWave * W) {
+            if (i + W <= len) {
+                Acc v[W];
+                load_vec<V, W>(src + s + i, v);
+#pragma unroll
+                for (int j = 0; j < W; ++j) st[i + j] = f(v[j], i + j);
+            } else {
+                for (int j = i; j < len; ++j) st[j] = f(VT<V>::up(src[s + j]), j);
+            }
+        }
+    } else if (perm == nullptr) {
+        for (int i = lane; i < len; i += kWave) st[i] = f(VT<V>::up(src[s + i]), i);
+    } else {
+        for (int i = lane; i < len; i += kWave) st[i] = f(VT<V>::up(src[(int64_t)perm[s + i]]), i);
+    }
+}
+
+// The head rule: entry s of the range that starts at s belongs to a group that started in an earlier range when ga — the first
+// group that starts at or after s — starts after s.  The head piece then ends at ptr[ga] or at the range's end.
+template <typename I>
+__device__ __forceinline__ bool seg_has_head(const I* __restrict__ ptr, int64_t n_groups, int64_t nnz, int64_t s, int64_t ga) {
+    return s < nnz && (ga == n_groups || (int64_t)ptr[ga] > s);
+}
+
+// One wave over its staged range w: the head piece, then the owned groups [ga, gb) — first entry in [s, e); the last range also
+// owns the empty groups at the end.  `part`: the range's workspace slots, or null when the caller knows that no group crosses a
+// range boundary; with it, tail[w] becomes the owned group that runs past the range, or -1.
+template <typename Op, typename I>
+__device__ __forceinline__ void seg_walk(typename Op::Acc* st, const I* __restrict__ ptr, int64_t n_groups, int64_t nnz, int64_t n_ranges,
+                                         int64_t w, int lane, typename Op::Acc* part, int64_t* tail, const Op op) {
+    using Part = typename Op::Part;
+    constexpr int R = lse_range<typename Op::Acc>();
+    const int64_t s = w * R, e = s + R < nnz ? s + R : nnz;
+    const int64_t ga = wave_lower_bound(ptr, n_groups, s, lane);
+    const int64_t gb = w == n_ranges - 1 ? n_groups : wave_lower_bound(ptr, n_groups, e, lane);
+
+    const bool head = seg_has_head(ptr, n_groups, nnz, s, ga);
+    if (head && part) {
+        const int64_t hend = (int64_t)ptr[ga];
+        const Part p = op.wave_reduce(st, 0, (int)((hend < e ? hend : e) - s), lane);
+        if (lane == 0) Op::put(part, p);
+    }
+    int64_t tailg = -1;   // (wave-uniform)
+
+    for (int64_t base = ga; base < gb; base += kWave) {
+        const int64_t g = base + lane;
+        const bool active = g < gb;
+        const int64_t glo = active ? (int64_t)ptr[g] : s;
+        const int64_t ghi = active ? (int64_t)ptr[g + 1] : s;
+        const int lo = (int)(glo - s), hi = (int)((ghi < e ? ghi : e) - s);
+        const bool wide = active && hi - lo > kLseLaneMax;
+        if (active && !wide) {
+            const Part p = op.lane_reduce(st, lo, hi);
+            if (ghi <= e) op.lane_finish(st, lo, hi, g, ghi - glo, p);
+            else if (part) Op::put(part + kSegTail, p);
+        }
+        const unsigned long long tmask = __ballot(active && !wide && ghi > e);
+        if (tmask) tailg = base + __builtin_ctzll(tmask);
+        unsigned long long mask = __ballot(wide);
+        while (mask) {
+            const int f = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int flo = __shfl(lo, f, kWave), fhi = __shfl(hi, f, kWave);
+            const int64_t fglo = __shfl(glo, f, kWave), fghi = __shfl(ghi, f, kWave);
+            const Part p = op.wave_reduce(st, flo, fhi, lane);
+            if (fghi <= e) {
+                op.wave_finish(st, flo, fhi, base + f, fghi - fglo, p, lane);
+            } else {
+                if (lane == 0 && part) Op::put(part + kSegTail, p);
+                tailg = base + f;
+            }
+        }
+    }
+    if (lane == 0 && part) tail[w] = tailg;
+}
+
+// One wave per range: the range's tail group (if any) merges its partials — the range's tail slot, then the head slots of the
+// later ranges it reaches — lane-strided and then across the wave in a fixed order; lane 0 finishes the group at that tail slot.
+template <typename Op, typename I>
+__global__ void __launch_bounds__(kBlock) seg_merge_kernel(typename Op::Params P) {
+    using Acc = typename Op::Acc;
+    constexpr int R = lse_range<Acc>();
+    const int lane = threadIdx.x % kWave;
+    const int64_t w = (int64_t)blockIdx.x * kLseWavesPerBlock + threadIdx.x / kWave;
+    if (w >= P.n_ranges) return;
+    const int64_t g = P.tail[w];
+    if (g < 0) return;
+    const I* __restrict__ ptr = static_cast<const I*>(P.ptr);
+    const int64_t glo = (int64_t)ptr[g], ghi = (int64_t)ptr[g + 1];
+    const int64_t w1 = (ghi - 1) / R;
+    Acc* part = static_cast<Acc*>(P.part);
+    typename Op::Part p = Op::identity();
+    for (int64_t j = lane; j <= w1 - w; j += kWave)
+        Op::combine(p, Op::get(j == 0 ? part + w * kSegSlots + kSegTail : part + (w + j) * kSegSlots));
+    p = Op::wave_combine(p);
+    // (the only reader of this slot above is lane 0 itself)
+    if (lane == 0) Op::merged_finish(P, part + w * kSegSlots + kSegTail, g, ghi - glo, p);
+}
+
+// One wave per range, for operators with one value per entry: the entries of its head piece (from the tail slot of the range that
+// owns that group) and of its tail piece, read once more from global memory.
+template <typename Op, typename I>
+__global__ void __launch_bounds__(kBlock) seg_fix_kernel(typename Op::Params P) {
+    using Acc = typename Op::Acc;
+    constexpr int R = lse_range<Acc>();
+    const int lane = threadIdx.x % kWave;
+    const int64_t w = (int64_t)blockIdx.x * kLseWavesPerBlock + threadIdx.x / kWave;
+    if (w >= P.n_ranges) return;
+    const I* __restrict__ ptr = static_cast<const I*>(P.ptr);
+    const I* __restrict__ perm = static_cast<const I*>(P.perm);
+    const Acc* part = static_cast<const Acc*>(P.part);
+    const int64_t s = w * R, e = s + R < P.nnz ? s + R : P.nnz;
+    auto piece = [&](int64_t lo, int64_t hi, int64_t owner) {
+        const auto t = Op::merged(part + owner * kSegSlots + kSegTail);
+        for (int64_t k = lo + lane; k < hi; k += kWave) Op::fix(P, perm ? (int64_t)perm[k] : k, t);
+    };
+    const int64_t tg = P.tail[w];
+    if (w > 0) {   // (range 0 has no head; the search is skipped where the range starts on a group start)
+        const int64_t ga = wave_lower_bound(ptr, P.n_groups, s, lane);
+        if (seg_has_head(ptr, P.n_groups, P.nnz, s, ga)) {
+            const int64_t hend = (int64_t)ptr[ga];
+            piece(s, hend < e ? hend : e, (int64_t)ptr[ga - 1] / R);
+        }
+    }
+    if (tg >= 0) piece((int64_t)ptr[tg], e, w);
+}
+
+// The (max, Σ exp) partial of log-sum-exp and of the softmax forward.  Max first and then the sum; across the wave the xor
+// butterfly with nanmax, then group_sum.
+template <typename A>
+struct MaxSumExp {
+    using Acc = A;
+    struct Part {
+        Acc m, s;
+    };
+    static __device__ __forceinline__ Part identity() { return {-(Acc)INFINITY, Acc(0)}; }
+    static __device__ __forceinline__ void combine(Part& a, Part b) { lse_combine(a.m, a.s, b.m, b.s); }
+    static __device__ __forceinline__ Part wave_combine(Part p) {
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const Acc m2 = shfl_xor_acc(p.m, o), s2 = shfl_xor_acc(p.s, o);
+            lse_combine(p.m, p.s, m2, s2);
+        }
+        return p;
+    }
+    static __device__ __forceinline__ void put(Acc* slot, Part p) {
+        slot[0] = p.m;
+        slot[1] = p.s;
+    }
+    static __device__ __forceinline__ Part get(const Acc* slot) { return {slot[0], slot[1]}; }
+    static __device__ __forceinline__ Part lane_reduce(const Acc* st, int lo, int hi) {
+        Acc m = -(Acc)INFINITY;
+        for (int i = lo; i < hi; ++i) m = nanmax(m, st[i]);
+        Acc sum = Acc(0);
+        if (finite_acc(m)) {
+            for (int i = lo; i < hi; ++i) sum += acc_exp(st[i] - m);
+        }
+        return {m, sum};
+    }
+    static __device__ __forceinline__ Part wave_reduce(const Acc* st, int lo, int hi, int lane) {
+        Acc m = -(Acc)INFINITY;
+        for (int i = lo + lane; i < hi; i += kWave) m = nanmax(m, st[i]);
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) m = nanmax(m, shfl_xor_acc(m, o));
+        Acc sum = Acc(0);
+        if (finite_acc(m)) {
+            for (int i = lo + lane; i < hi; i += kWave) sum += acc_exp(st[i] - m);
+        }
+        return {m, group_sum<Acc, kWave>(sum)};
+    }
+};
+
+// ---- log-sum-exp forward -------------------------------------------------------------------------------------------------
 template <typename V>
 struct LseFwd {
     const void* ptr;     // [n_groups + 1]
     const void* perm;    // [nnz] or null: entry k is val[perm[k]]
     const V* val;
     V* out;
-    void* part;          // Acc[n_ranges][4]: head (m, s), tail (m, s)
+    void* part;          // Acc[n_ranges][kSegSlots]: head (m, s), tail (m, s)
     int64_t* tail;       // [n_ranges]: the owned group that runs past the range, or -1
     int64_t n_groups, nnz, n_ranges;
     int64_t axis_len;    // entries per group including the absent ones; < 0: absent entries do not count
@@ -113,11 +319,28 @@ __device__ __forceinline__ int64_t lse_zeros(const LseFwd<V>& P, int64_t count) 
     return P.axis_len < 0 ? 0 : P.axis_len - count;
 }
 
+// A finished group is one value, written by one lane.
+template <typename V>
+struct LseOp : MaxSumExp<typename VT<V>::Acc> {
+    using Acc = typename VT<V>::Acc;
+    using Part = typename MaxSumExp<Acc>::Part;
+    using Params = LseFwd<V>;
+    const Params& P;
+    __device__ __forceinline__ explicit LseOp(const Params& p) : P(p) {}
+    static __device__ __forceinline__ void store_group(const Params& P, int64_t g, int64_t count, Part p) {
+        lse_store(P, g, lse_finish(p.m, p.s, lse_zeros(P, count)));
+    }
+    __device__ __forceinline__ void lane_finish(Acc*, int, int, int64_t g, int64_t count, Part p) const { store_group(P, g, count, p); }
+    __device__ __forceinline__ void wave_finish(Acc*, int, int, int64_t g, int64_t count, Part p, int lane) const {
+        if (lane == 0) store_group(P, g, count, p);
+    }
+    static __device__ __forceinline__ void merged_finish(const Params& P, Acc*, int64_t g, int64_t count, Part p) { store_group(P, g, count, p); }
+};
+
 template <typename V, typename I>
 __global__ void __launch_bounds__(kBlock) lse_fwd_kernel(LseFwd<V> P) {
     using Acc = typename VT<V>::Acc;
     constexpr int R = lse_range<Acc>();
-    constexpr int W = VT<V>::kWide;
     __shared__ Acc stage[kLseWavesPerBlock][R];
     const int lane = threadIdx.x % kWave, wid = threadIdx.x / kWave;
     const I* __restrict__ ptr = static_cast<const I*>(P.ptr);
@@ -132,138 +355,14 @@ __global__ void __launch_bounds__(kBlock) lse_fwd_kernel(LseFwd<V> P) {
 
     const int64_t w = (int64_t)blockIdx.x * kLseWavesPerBlock + wid;
     const bool live = w < P.n_ranges;   // (every wave reaches the barrier below)
-    const int64_t s = w * R;
-    const int64_t e = !live ? s : s + R < P.nnz ? s + R : P.nnz;
-    const int len = (int)(e - s);
-    const bool last = w == P.n_ranges - 1;
     Acc* st = stage[wid];
-
-    // stage the range
-    if (perm == nullptr && P.vec_ok) {
-        const V* src = P.val + s;
-        for (int i = lane * W; i < len; i += kWave * W) {
-            if (i + W <= len) {
-                Acc v[W];
-                load_vec<V, W>(src + i, v);
-#pragma unroll
-                for (int j = 0; j < W; ++j) st[i + j] = v[j];
-            } else {
-                for (int j = i; j < len; ++j) st[j] = VT<V>::up(src[j]);
-            }
-        }
-    } else if (perm == nullptr) {
-        for (int i = lane; i < len; i += kWave) st[i] = VT<V>::up(P.val[s + i]);
-    } else {
-        for (int i = lane; i < len; i += kWave) st[i] = VT<V>::up(P.val[(int64_t)perm[s + i]]);
-    }
-
+    seg_stage<V, I>(st, P.val, perm, w * R, live ? seg_len<Acc>(w, P.nnz) : 0, P.vec_ok != 0, lane, [](Acc v, int) { return v; });
     __syncthreads();
     if (!live) return;
-    // owned groups [ga, gb): first entry in [s, e) (the last range also owns the empty groups at the end)
-    const int64_t ga = wave_lower_bound(ptr, P.n_groups, s, lane);
-    const int64_t gb = last ? P.n_groups : wave_lower_bound(ptr, P.n_groups, e, lane);
-
-    Acc* part = static_cast<Acc*>(P.part) + w * 4;
-    const Acc ninf = -(Acc)INFINITY;
-
-    // the whole wave over st[lo, hi): (m, s) in every lane
-    auto wave_reduce = [&](int lo, int hi, Acc& m, Acc& sum) {
-        m = ninf;
-        for (int i = lo + lane; i < hi; i += kWave) m = nanmax(m, st[i]);
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) m = nanmax(m, shfl_xor_acc(m, o));
-        sum = Acc(0);
-        if (finite_acc(m)) {
-            for (int i = lo + lane; i < hi; i += kWave) sum += acc_exp(st[i] - m);
-        }
-        sum = group_sum<Acc, kWave>(sum);
-    };
-
-    // head: the group entry s belongs to started in an earlier range
-    if (s < P.nnz && (ga == P.n_groups || (int64_t)ptr[ga] > s)) {
-        const int64_t hend = (int64_t)ptr[ga];
-        Acc m, sum;
-        wave_reduce(0, (int)((hend < e ? hend : e) - s), m, sum);
-        if (lane == 0) {
-            part[0] = m;
-            part[1] = sum;
-        }
-    }
-    int64_t tailg = -1;   // (wave-uniform)
-
-    for (int64_t base = ga; base < gb; base += kWave) {
-        const int64_t g = base + lane;
-        const bool active = g < gb;
-        const int64_t glo = active ? (int64_t)ptr[g] : s;
-        const int64_t ghi = active ? (int64_t)ptr[g + 1] : s;
-        const int lo = (int)(glo - s), hi = (int)((ghi < e ? ghi : e) - s);
-        const bool wide = active && hi - lo > kLseLaneMax;
-        if (active && !wide) {
-            Acc m = ninf;
-            for (int i = lo; i < hi; ++i) m = nanmax(m, st[i]);
-            Acc sum = Acc(0);
-            if (finite_acc(m)) {
-                for (int i = lo; i < hi; ++i) sum += acc_exp(st[i] - m);
-            }
-            if (ghi <= e) {
-                lse_store(P, g, lse_finish(m, sum, lse_zeros(P, ghi - glo)));
-            } else {
-                part[2] = m;
-                part[3] = sum;
-            }
-        }
-        const unsigned long long tmask = __ballot(active && !wide && ghi > e);
-        if (tmask) tailg = base + __builtin_ctzll(tmask);
-        unsigned long long mask = __ballot(wide);
-        while (mask) {
-            const int f = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const int flo = __shfl(lo, f, kWave), fhi = __shfl(hi, f, kWave);
-            const int64_t fglo = __shfl(glo, f, kWave), fghi = __shfl(ghi, f, kWave);
-            Acc m, sum;
-            wave_reduce(flo, fhi, m, sum);
-            if (lane == 0) {
-                if (fghi <= e) {
-                    lse_store(P, base + f, lse_finish(m, sum, lse_zeros(P, fghi - fglo)));
-                } else {
-                    part[2] = m;
-                    part[3] = sum;
-                }
-            }
-            if (fghi > e) tailg = base + f;
-        }
-    }
-    if (lane == 0) P.tail[w] = tailg;
+    seg_walk(st, ptr, P.n_groups, P.nnz, P.n_ranges, w, lane, static_cast<Acc*>(P.part) + w * kSegSlots, P.tail, LseOp<V>(P));
 }
 
-// One wave per range: the range's tail group (if any) merges its partials — the range's tail slot, then the head slots of the
-// later ranges it reaches — lane-strided and then by a fixed butterfly; lane 0 writes the group.
-template <typename V, typename I>
-__global__ void __launch_bounds__(kBlock) lse_merge_kernel(LseFwd<V> P) {
-    using Acc = typename VT<V>::Acc;
-    constexpr int R = lse_range<Acc>();
-    const int lane = threadIdx.x % kWave;
-    const int64_t w = (int64_t)blockIdx.x * kLseWavesPerBlock + threadIdx.x / kWave;
-    if (w >= P.n_ranges) return;
-    const int64_t g = P.tail[w];
-    if (g < 0) return;
-    const I* __restrict__ ptr = static_cast<const I*>(P.ptr);
-    const int64_t glo = (int64_t)ptr[g], ghi = (int64_t)ptr[g + 1];
-    const int64_t w1 = (ghi - 1) / R;
-    const Acc* part = static_cast<const Acc*>(P.part);
-    Acc m = -(Acc)INFINITY, sum = Acc(0);
-    for (int64_t j = lane; j <= w1 - w; j += kWave) {
-        const Acc* q = j == 0 ? part + w * 4 + 2 : part + (w + j) * 4;
-        lse_combine(m, sum, q[0], q[1]);
-    }
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const Acc m2 = shfl_xor_acc(m, o), s2 = shfl_xor_acc(sum, o);
-        lse_combine(m, sum, m2, s2);
-    }
-    if (lane == 0) lse_store(P, g, lse_finish(m, sum, lse_zeros(P, ghi - glo)));
-}
-
+// ---- log-sum-exp backward ------------------------------------------------------------------------------------------------
 template <typename V>
 struct LseBwd {
     const void* ptr;      // [n1 + 1] primary groups in stored order, or null
@@ -354,6 +453,33 @@ __global__ void __launch_bounds__(kBlock) lse_bwd_kernel(LseBwd<V> P) {
         for (int j = 0; j < W; ++j)
             if (k0 + j < e) P.grad[k0 + j] = VT<V>::down(out[j]);
     }
+}
+
+// ---- host side: ranges and the workspace of the walk ----------------------------------------------------------------------
+// entries per range of a value type; -1: not a value type of these kernels
+inline int64_t seg_range_of(int vtype) {
+    if (vtype == TSGU_F32 || vtype == TSGU_BF16) return lse_range<float>();
+    if (vtype == TSGU_F64) return lse_range<double>();
+    return -1;
+}
+
+inline int64_t seg_ranges(int64_t range, int64_t nnz) { return nnz > 0 ? (nnz + range - 1) / range : 1; }
+
+// workgroups of a kernel with one wave per range
+inline int64_t seg_blocks(int64_t n_ranges) { return (n_ranges + kLseWavesPerBlock - 1) / kLseWavesPerBlock; }
+
+// Acc[n_ranges][kSegSlots] and the tail groups int64[n_ranges]; -1: not a value type
+inline int64_t seg_ws_bytes(int vtype, int64_t nnz) {
+    const int64_t range = seg_range_of(vtype);
+    if (range < 0) return -1;
+    return seg_ranges(range, nnz) * (int64_t)(kSegSlots * (kLseStageBytes / range) + sizeof(int64_t));
+}
+
+// point `part` and `tail` of a parameter block (n_ranges set) into the workspace; both null without one
+template <typename Acc, typename Params>
+inline void seg_set_workspace(Params& p, void* workspace) {
+    p.part = workspace;
+    p.tail = workspace ? reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + p.n_ranges * kSegSlots * sizeof(Acc)) : nullptr;
 }
 
 }  // namespace tsgu
