@@ -202,6 +202,15 @@ SIGNATURES_SPGEMM = {
         _int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_bsr.h (same library, same ABI version)
+SIGNATURES_BSR = {
+    "tsgu_bsr_mm_geometry": (_int, [_int, _i64, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_bsr_spmm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
+    "tsgu_bsr_sddmm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _ptr, _int, _ptr]),
+    "tsgu_bsr_spmm_t": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -225,7 +234,7 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
-                                  *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items()):
+                                  *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items(), *SIGNATURES_BSR.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -970,6 +979,69 @@ def csr_spmm_reduce_backward_dense(tptr, tidx, perm, val, arg, G, n_rows: int, n
     dB = torch.empty((n_cols, p), dtype=G.dtype, device=dev)
     launch("tsgu_csr_spmm_reduce_backward_dense", dev, vtype_of(G), itype_of(tptr), n_rows, n_cols, tidx.numel(), tptr, tidx, perm,
            val, arg, _ld(arg), G, _ld(G), p, dB, p)
+    return dB
+
+
+def bsr_mm_geometry(dtype: torch.dtype, bh: int, bw: int, p: int):
+    """(rows of the result per workgroup, columns of the p per workgroup, summed elements per LDS stage) of the block-sparse product
+    kernels for blocks of bh × bw elements of `dtype` against `p` dense columns: the sizes at which their walk changes path.  Host only."""
+    rows, cols, stage = _int(0), _int(0), _int(0)
+    check(load_library().tsgu_bsr_mm_geometry(_VTYPE[dtype], int(bh), int(bw), int(p), ctypes.byref(rows), ctypes.byref(cols),
+                                              ctypes.byref(stage)), "tsgu_bsr_mm_geometry")
+    return int(rows.value), int(cols.value), int(stage.value)
+
+
+def _bsr_operands(index_arrays, val, *dense):
+    dev = require_device(*index_arrays, val, *dense)
+    first = index_arrays[0]
+    for t in index_arrays:
+        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
+            raise RuntimeError("the index arrays of a block-sparse product must be contiguous 1-D arrays of one dtype")
+    ref = dense[0]
+    for t in dense:
+        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1) or (t.stride(1) != 1 and t.size(1) > 1) or (
+                t.size(0) > 1 and t.stride(0) < t.size(1)):
+            raise RuntimeError("the dense operands of a block-sparse product must be 2-D row-major arrays of one dtype and width")
+    if ref.size(1) < 1:
+        raise RuntimeError("the block-sparse product needs at least one column")
+    if val is not None and (val.dtype != ref.dtype or val.dim() != 3 or not val.is_contiguous()):
+        raise RuntimeError(f"the blocks must be a contiguous (nnzb, bh, bw) array of the dense operands' dtype {ref.dtype}, "
+                           f"got {tuple(val.shape)} of {val.dtype}")
+    return dev
+
+
+def bsr_spmm(crow, col, val, B, n_block_rows: int, n_block_cols: int):
+    """C [n_block_rows·bh, p] = A·B for the 2-D BSR arrays (crow, col, val [nnzb, bh, bw]) and B [n_block_cols·bw, p]."""
+    dev = _bsr_operands((crow, col), val, B)
+    nnzb, bh, bw = val.shape
+    p = B.size(1)
+    C = torch.empty((n_block_rows * bh, p), dtype=B.dtype, device=dev)
+    if C.numel():
+        launch("tsgu_bsr_spmm", dev, vtype_of(B), itype_of(crow), n_block_rows, n_block_cols, nnzb, bh, bw, crow, col, val, B, _ld(B),
+               p, C, p)
+    return C
+
+
+def bsr_sddmm(crow, col, G, B, n_block_rows: int, n_block_cols: int, bh: int, bw: int):
+    """dval [nnzb, bh, bw]: dval[e] = G[I_e·bh : +bh] · B[col[e]·bw : +bw]ᵀ, in the order of the value array."""
+    dev = _bsr_operands((crow, col), None, G, B)
+    nnzb = col.numel()
+    dval = torch.empty((nnzb, bh, bw), dtype=B.dtype, device=dev)
+    if nnzb:
+        launch("tsgu_bsr_sddmm", dev, vtype_of(B), itype_of(crow), n_block_rows, n_block_cols, nnzb, bh, bw, crow, col, G, _ld(G), B,
+               _ld(B), G.size(1), dval)
+    return dval
+
+
+def bsr_spmm_t(tptr, tidx, perm, val, G, n_block_rows: int, n_block_cols: int):
+    """dB [n_block_cols·bw, p] = Aᵀ·G over the transposed block walk (tptr, tidx, perm into val [nnzb, bh, bw])."""
+    dev = _bsr_operands((tptr, tidx, perm), val, G)
+    nnzb, bh, bw = val.shape
+    p = G.size(1)
+    dB = torch.empty((n_block_cols * bw, p), dtype=G.dtype, device=dev)
+    if dB.numel():
+        launch("tsgu_bsr_spmm_t", dev, vtype_of(G), itype_of(tptr), n_block_rows, n_block_cols, nnzb, bh, bw, tptr, tidx, perm, val, G,
+               _ld(G), p, dB, p)
     return dB
 
 

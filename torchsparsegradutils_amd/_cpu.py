@@ -24,6 +24,8 @@ nested-tensor ``segment_mm`` / ``gather_mm``        :func:`segment_mm` / :func:`
                                            :func:`segment_softmax` per head, ``index_add``
 ``torch.sparse.mm(A, B, reduce)`` (ATen)   :func:`mm_reduce` / :func:`mm_reduce_backward` on the 2-D CSR arrays
 ``torch.sparse.mm(S1, S2)`` (ATen)         :func:`spgemm` / :func:`spgemm_backward` on coalesced COO operands
+(none: torch's CPU BSR product refuses     :func:`bsr_mm` / :func:`bsr_mm_backward`: gather the slabs of ``B`` by block column,
+  non-square blocks and bfloat16)          ``torch.bmm``, ``index_add_`` by block row — and the mirror for the gradients
 =========================================  ====================================================================
 """
 
@@ -414,3 +416,45 @@ def spgemm_backward(A: torch.Tensor, B: torch.Tensor, G: torch.Tensor, need_a: b
             raise RuntimeError("torch.sparse.mm returned a gradient that is not on its operand's pattern")
         out.append(g._values())
     return out[0], out[1]
+
+
+def _bsr_acc(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def bsr_mm(plan: _pt.RowGather, blocks: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """A·B for the 2-D block pattern `plan` with `blocks` (nnzb, bh, bw) and B (n_block_cols·bw, p): the slabs of B gathered by block
+    column, one ``torch.bmm``, ``index_add_`` by block row (a block row's blocks in stored order).  Every stored block is a term.
+    Accumulated in float32 for float32 and bfloat16 (rounded once), in float64 for float64.  No torch BSR product is called."""
+    _cpu_only(plan.crow, blocks, B)
+    nnzb, bh, bw = blocks.shape
+    p = B.size(-1)
+    acc = _bsr_acc(B.dtype)
+    out = torch.zeros((plan.n_rows, bh, p), dtype=acc)
+    if nnzb:
+        slabs = B.reshape(plan.n_cols, bw, p).index_select(0, plan.col.to(torch.int64)).to(acc)
+        out.index_add_(0, plan.row_indices().to(torch.int64), torch.bmm(blocks.to(acc), slabs))
+    return out.reshape(plan.n_rows * bh, p).to(B.dtype)
+
+
+def bsr_mm_backward(plan: _pt.RowGather, blocks: torch.Tensor, B: torch.Tensor, G: torch.Tensor, need_a: bool, need_b: bool):
+    """(gradient of the blocks or None, gradient of B or None) of :func:`bsr_mm`: its mirror — dV[e] = G[I_e] · B[J_e]ᵀ per stored
+    block, and dB = Aᵀ·G by ``index_add_`` of V[e]ᵀ · G[I_e] by block column."""
+    _cpu_only(plan.crow, blocks, B, G)
+    nnzb, bh, bw = blocks.shape
+    p = B.size(-1)
+    acc = _bsr_acc(B.dtype)
+    rows, cols = plan.row_indices().to(torch.int64), plan.col.to(torch.int64)
+    g_slabs = G.reshape(plan.n_rows, bh, p).index_select(0, rows).to(acc) if nnzb else None
+    dblocks = dB = None
+    if need_a:
+        dblocks = torch.zeros((nnzb, bh, bw), dtype=B.dtype)
+        if nnzb:
+            b_slabs = B.reshape(plan.n_cols, bw, p).index_select(0, cols).to(acc)
+            dblocks = torch.bmm(g_slabs, b_slabs.transpose(1, 2)).to(B.dtype)
+    if need_b:
+        out = torch.zeros((plan.n_cols, bw, p), dtype=acc)
+        if nnzb:
+            out.index_add_(0, cols, torch.bmm(blocks.to(acc).transpose(1, 2), g_slabs))
+        dB = out.reshape(plan.n_cols * bw, p).to(B.dtype)
+    return dblocks, dB

@@ -1008,6 +1008,15 @@ def from_csr(A: torch.Tensor) -> RowGather:
     return RowGather(crow, col, A.size(-2), A.size(-1), core=_core_for("csr", (crow, col), A.shape))
 
 
+def from_bsr(A: torch.Tensor) -> RowGather:
+    """Plan for a BSR tensor, 2-D or batched 3-D: (crow, col) is the CSR pattern of the (n / bh) × (m / bw) block matrix, so the
+    row gather, its cache, ``.transposed`` (``perm`` = a block's position in the value array) and ``flat_of`` apply unchanged.  The
+    block size is part of the key: the same index tensors under another block size are another matrix."""
+    crow, col = A.crow_indices(), A.col_indices()
+    bh, bw = A.values().shape[-2:]
+    return RowGather(crow, col, A.size(-2) // bh, A.size(-1) // bw, core=_core_for("bsr", (crow, col), tuple(A.shape) + (bh, bw)))
+
+
 def from_csc(A: torch.Tensor) -> RowGather:
     """Plan for a CSC tensor, 2-D or batched 3-D: its columns as the groups of a row gather (ccol, row_indices) of Aᵀ, so that
     ``.transposed`` walks A's rows (with a ``perm`` into A's value array)."""
