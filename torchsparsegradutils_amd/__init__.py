@@ -2,8 +2,8 @@
 
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
-and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm``
-beside them;
+and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
+``sparse_bsr_attention`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -12,6 +12,7 @@ from ._compat import linalg_solve_triangular_compat
 from ._pattern import wait_for_plans
 from .indexed_matmul import GatherMM, SegmentMM, gather_mm, segment_mm
 from .sparse_attention import SparseAttention, sparse_attention
+from .sparse_bsr_attention import SparseBSRAttention, sparse_bsr_attention
 from .sparse_bsr_mm import SparseBSRMatMul, sparse_bsr_mm
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
@@ -31,6 +32,7 @@ __all__ = [
     "sparse_mm_reduce",
     "sparse_spgemm",
     "sparse_bsr_mm",
+    "sparse_bsr_attention",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",
@@ -48,6 +50,7 @@ __all__ = [
     "SparseMMReduce",
     "SparseSpGEMM",
     "SparseBSRMatMul",
+    "SparseBSRAttention",
     "SparseTriangularSolve",
     "SparseGenericSolve",
     "SparseLogSumExp",

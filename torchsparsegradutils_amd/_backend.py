@@ -211,6 +211,21 @@ SIGNATURES_BSR = {
         _int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_bsr_attention.h (same library, same ABI version)
+SIGNATURES_BSR_ATTENTION = {
+    "tsgu_bsr_attention_supported": (_int, [_int, _int, _int, _i64, _i64]),
+    "tsgu_bsr_attention_geometry": (_int, [_int, _int, _int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_bsr_attention": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _int, _int, _dbl, _ptr,
+               _i64, _ptr, _ptr, _int, _ptr]),
+    "tsgu_bsr_attention_backward_rows": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64,
+               _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _ptr, _int, _ptr]),
+    "tsgu_bsr_attention_backward_cols": (
+        _int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr,
+               _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _i64, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -234,7 +249,8 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
-                                  *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items(), *SIGNATURES_BSR.items()):
+                                  *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items(), *SIGNATURES_BSR.items(),
+                                  *SIGNATURES_BSR_ATTENTION.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -1043,6 +1059,85 @@ def bsr_spmm_t(tptr, tidx, perm, val, G, n_block_rows: int, n_block_cols: int):
         launch("tsgu_bsr_spmm_t", dev, vtype_of(G), itype_of(tptr), n_block_rows, n_block_cols, nnzb, bh, bw, tptr, tidx, perm, val, G,
                _ld(G), p, dB, p)
     return dB
+
+
+BSR_ATTENTION_LIMITS = "block sides that are multiples of 16, d in {16, 32, 64, 128} and H >= 1"
+
+
+def bsr_attention_supported(dtype: torch.dtype, heads: int, d: int, bh: int, bw: int) -> bool:
+    """Do the block-sparse attention kernels take `heads` heads of width `d` over blocks of bh × bw in value type `dtype`?  Host only."""
+    vt = _VTYPE.get(dtype)
+    return vt is not None and bool(load_library().tsgu_bsr_attention_supported(vt, int(heads), int(d), int(bh), int(bw)))
+
+
+def bsr_attention_geometry(dtype: torch.dtype, heads: int, d: int, bh: int, bw: int):
+    """(rows one workgroup owns, keys of one LDS stage) of the block-sparse attention kernels: the sizes at which their walk
+    changes path.  Host only."""
+    rows, stage = _int(0), _int(0)
+    check(load_library().tsgu_bsr_attention_geometry(_VTYPE[dtype], int(heads), int(d), int(bh), int(bw), ctypes.byref(rows),
+                                                     ctypes.byref(stage)), "tsgu_bsr_attention_geometry")
+    return int(rows.value), int(stage.value)
+
+
+def _bsr_attention_operands(index_arrays, bias, bh: int, bw: int, *dense):
+    dev = require_device(*index_arrays, bias, *dense)
+    first = index_arrays[0]
+    for t in index_arrays:
+        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
+            raise RuntimeError("the index arrays of a block-sparse attention must be contiguous 1-D arrays of one dtype")
+    ref = dense[0]
+    for t in dense:
+        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1):
+            raise RuntimeError("the dense operands must be 2-D [rows, heads*d] of one dtype and width")
+    if bias is not None and (bias.dtype != ref.dtype or bias.dim() != 3 or tuple(bias.shape[1:]) != (bh, bw) or not bias.is_contiguous()):
+        raise RuntimeError(f"the bias must be a contiguous (nnzb, {bh}, {bw}) array of the dense operands' dtype {ref.dtype}")
+    return dev
+
+
+def bsr_attention(crow, col, bias, bh: int, bw: int, Q, K, V, heads: int, d: int, scale: float, want_acc: bool = True):
+    """(O [n, heads·d], lse [n, heads] in the accumulator type, O before its rounding — O itself unless bfloat16) of attention over
+    the 2-D block pattern (crow, col) of bh × bw blocks; bias: the stored blocks [nnzb, bh, bw] or None.  want_acc=False (no backward
+    will follow) spares bfloat16 the second accumulator; the third result is then O."""
+    dev = _bsr_attention_operands((crow, col), bias, bh, bw, Q, K, V)
+    Q, K, V = _aligned_rows(Q), _aligned_rows(K), _aligned_rows(V)
+    nrb, ncb = crow.numel() - 1, K.size(0) // bw
+    O = torch.empty((nrb * bh, heads * d), dtype=Q.dtype, device=dev)
+    lse = torch.empty((nrb * bh, heads), dtype=_acc_dtype(Q.dtype), device=dev)
+    Oacc = torch.empty((nrb * bh, heads * d), dtype=lse.dtype, device=dev) if want_acc and O.dtype != lse.dtype else None
+    if O.numel():
+        launch("tsgu_bsr_attention", dev, vtype_of(Q), itype_of(crow), nrb, ncb, col.numel(), bh, bw, crow, col, bias, Q, _ld(Q), K,
+               _ld(K), V, _ld(V), heads, d, float(scale), O, _ld(O), lse, Oacc)
+    return O, lse, (O if Oacc is None else Oacc)
+
+
+def bsr_attention_backward(crow, col, twalk, bias, bh: int, bw: int, Q, K, V, dO, O, lse, heads: int, d: int, scale: float,
+                           want_dA: bool):
+    """(dQ, dK, dV, dA or None) from the forward's O (in the accumulator type: its third result) and lse: the row pass over (crow, col), then the column pass over the transposed
+    block walk `twalk` = (tptr, tidx, perm) on the same stream.  dA is [nnzb, bh, bw] in the accumulator type."""
+    tptr, tidx, perm = twalk
+    dev = _bsr_attention_operands((crow, col, tptr, tidx, perm), bias, bh, bw, Q, K, V, dO)
+    require_device(O)
+    Q, K, V, dO, O = (_aligned_rows(x) for x in (Q, K, V, dO, O))
+    nrb, ncb, nnzb = crow.numel() - 1, tptr.numel() - 1, col.numel()
+    n, m = nrb * bh, ncb * bw
+    acc = _acc_dtype(Q.dtype)
+    if lse.dtype != acc or lse.shape != (n, heads) or not lse.is_contiguous():
+        raise RuntimeError("lse must be the forward's [n, heads] array in the accumulator type")
+    if O.dtype != acc or O.shape != (n, heads * d):
+        raise RuntimeError("O must be the forward's [n, heads*d] result in the accumulator type")
+    dQ = torch.empty((n, heads * d), dtype=Q.dtype, device=dev)
+    dK = torch.empty((m, heads * d), dtype=Q.dtype, device=dev)
+    dV = torch.empty((m, heads * d), dtype=Q.dtype, device=dev)
+    delta = torch.empty((n, heads), dtype=acc, device=dev)
+    dA = torch.empty((nnzb, bh, bw), dtype=acc, device=dev) if want_dA else None
+    vt, it = vtype_of(Q), itype_of(crow)
+    if n:
+        launch("tsgu_bsr_attention_backward_rows", dev, vt, it, nrb, ncb, nnzb, bh, bw, crow, col, bias, Q, _ld(Q), K, _ld(K), V,
+               _ld(V), dO, _ld(dO), O, _ld(O), lse, heads, d, float(scale), dQ, _ld(dQ), delta, dA)
+    if m:
+        launch("tsgu_bsr_attention_backward_cols", dev, vt, it, nrb, ncb, nnzb, bh, bw, tptr, tidx, perm, bias, Q, _ld(Q), K, _ld(K),
+               V, _ld(V), dO, _ld(dO), lse, delta, heads, d, float(scale), dK, _ld(dK), dV, _ld(dV))
+    return dQ, dK, dV, dA
 
 
 # kSpgemmLimit / kSpgemmGroup of csrc/spgemm_impl.h (tsgu_spgemm_bins reports them): the sparse × sparse kernels bin the rows of C by

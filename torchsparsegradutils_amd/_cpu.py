@@ -458,3 +458,42 @@ def bsr_mm_backward(plan: _pt.RowGather, blocks: torch.Tensor, B: torch.Tensor, 
             out.index_add_(0, cols, torch.bmm(blocks.to(acc).transpose(1, 2), g_slabs))
         dB = out.reshape(plan.n_cols * bw, p).to(B.dtype)
     return dblocks, dB
+
+
+def bsr_element_walk(plan: _pt.RowGather, bh: int, bw: int):
+    """(ptr, idx, perm) of the element pattern that the 2-D block pattern `plan` of bh × bw blocks covers, walked by rows: every
+    element row lists its block row's blocks in stored order, each block's bw columns in order; perm is the element's position in
+    the packed (nnzb, bh, bw) value array.  A repeated (I, J) lists its columns twice."""
+    crow, col = plan.crow.to(torch.int64), plan.col.to(torch.int64)
+    nrb = plan.n_rows
+    counts = (crow[1:] - crow[:-1]) * bw                                    # entries per element row, by block row
+    ptr = torch.zeros(nrb * bh + 1, dtype=torch.int64)
+    ptr[1:] = counts.repeat_interleave(bh).cumsum(0)
+    blocks = _segment_ids(crow, nrb, col.numel())                           # block row of every block
+    # entries of element row (I, r): for e in block row I, for c < bw -> built as (e, r, c) sorted by (I, r, e, c)
+    e = torch.arange(col.numel())
+    first = crow[blocks]                                                    # first block of e's block row
+    n_in_row = (crow[1:] - crow[:-1])[blocks]
+    r = torch.arange(bh).view(1, bh, 1)
+    c = torch.arange(bw).view(1, 1, bw)
+    # position of entry (e, r, c) in the walk: start of block row + r·(blocks in row)·bw + (e − first)·bw + c
+    start = ptr[:-1][blocks * bh].view(-1, 1, 1)
+    pos = start + r * (n_in_row * bw).view(-1, 1, 1) + ((e - first) * bw).view(-1, 1, 1) + c
+    idx = torch.empty(col.numel() * bh * bw, dtype=torch.int64)
+    perm = torch.empty_like(idx)
+    idx[pos.reshape(-1)] = (col.view(-1, 1, 1) * bw + c).expand(-1, bh, -1).reshape(-1)
+    perm[pos.reshape(-1)] = (e.view(-1, 1, 1) * (bh * bw) + r * bw + c).reshape(-1)
+    return ptr, idx, perm
+
+
+def bsr_attention(plan: _pt.RowGather, bias, bh: int, bw: int, Q, K, V, heads: int, scale: float):
+    """(O, (the element walk, P)) of block-sparse attention by :func:`attention` over the element pattern the blocks cover."""
+    walk = bsr_element_walk(plan, bh, bw)
+    O, P = attention(*walk, None if bias is None else bias.reshape(-1), Q, K, V, heads, scale)
+    return O, walk, P
+
+
+def bsr_attention_backward(walk, bh: int, bw: int, Q, K, V, dO, P, heads: int, scale: float, want_dA: bool):
+    """(dQ, dK, dV, dA [nnzb, bh, bw] or None) by :func:`attention_backward`; dA folded back into the blocks (perm)."""
+    dQ, dK, dV, dA = attention_backward(*walk, Q, K, V, dO, P, heads, scale, want_dA)
+    return dQ, dK, dV, (dA.view(-1, bh, bw) if want_dA else None)
