@@ -1,19 +1,13 @@
 // Block-sparse × dense products: the extern "C" entry points of include/tsgu_hip_bsr.h (kernels: bsr_impl.h, one instantiation
 // file per value type).
 #include "bsr_impl.h"
+#include "bsr_host.h"
 
 #include "../../include/tsgu_hip_bsr.h"
 
 using namespace tsgu;
 
 namespace {
-
-constexpr int64_t kI31 = 0x7fffffffLL;
-
-struct Dense {
-    const void* ptr;
-    int64_t ld;
-};
 
 // Whole aligned 16-byte lanes: a base on a 16-byte boundary and every listed count a multiple of the lane's elements.
 bool whole_lanes(int vtype, std::initializer_list<const void*> bases, std::initializer_list<int64_t> counts) {
@@ -25,26 +19,16 @@ bool whole_lanes(int vtype, std::initializer_list<const void*> bases, std::initi
     return true;
 }
 
-int elem_bytes(int vtype) { return vtype == TSGU_F32 ? 4 : vtype == TSGU_F64 ? 8 : vtype == TSGU_BF16 ? 2 : 0; }
-
-// The host-side refusals the three launchers share, in the order the header states.  `always`: pointers every call needs;
-// `stored`: those only a pattern with blocks dereferences.
+// The host-side refusals the three launchers share, in the order the header states.
 int bsr_check(int vtype, int itype, int64_t nrb, int64_t ncb, int64_t nnzb, int64_t bh, int64_t bw, int64_t p,
               std::initializer_list<const void*> always, std::initializer_list<const void*> stored, std::initializer_list<Dense> dense) {
-    for (const void* q : always)
-        if (!q) return TSGU_ERR_BAD_ARG;
-    for (const void* q : stored)
-        if (!q && nnzb > 0) return TSGU_ERR_BAD_ARG;
-    if (!elem_bytes(vtype) || (itype != TSGU_I32 && itype != TSGU_I64)) return TSGU_ERR_BAD_DTYPE;
+    if (const int rc = bsr_check_args(vtype, itype, nnzb, always, stored)) return rc;
     if (p < 1 || bh < 1 || bw < 1 || nrb < 0 || ncb < 0 || nnzb < 0) return TSGU_ERR_BAD_ARG;
     for (const Dense& o : dense) {
         if (o.ld < p) return TSGU_ERR_BAD_ARG;
         if (reinterpret_cast<uintptr_t>(o.ptr) % elem_bytes(vtype)) return TSGU_ERR_BAD_ARG;      // whole elements
     }
-    for (const Dense& o : dense)
-        if (o.ld > 0xffffffffLL) return TSGU_ERR_TOO_LARGE;
-    if (bh > kI31 || bw > kI31 || nnzb > kI31 / bh / bw || nrb > kI31 / bh || ncb > kI31 / bw) return TSGU_ERR_TOO_LARGE;
-    return TSGU_OK;
+    return bsr_check_sizes(nrb, ncb, nnzb, bh, bw, dense, false);
 }
 
 // Forward (trans = false: walks block rows, sums over bw) and transposed product (walks block columns, sums over bh).
@@ -53,15 +37,16 @@ int bsr_mm(int vtype, int itype, bool trans, int64_t n_groups, int64_t bh, int64
     if (n_groups == 0) return TSGU_OK;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t oh = trans ? bw : bh;
+    const BsrSplit split = bsr_tile_split(oh, kBsrTM, n_groups);
     return with_value_type<float, double, bf16_t>(vtype, [&](auto v) {
         using V = decltype(v);
         BsrMM<V> P{};
         P.ptr = ptr, P.idx = idx, P.perm = perm;
         P.val = static_cast<const V*>(val), P.D = static_cast<const V*>(D), P.out = static_cast<V*>(out);
         P.ldd = ldd, P.ldo = ldo, P.n_groups = n_groups, P.p = p, P.bh = bh, P.bw = bw;
-        P.oh = trans ? bw : bh, P.kb = trans ? bh : bw;
-        P.per_tile = P.oh <= kBsrTM ? kBsrTM / P.oh : 1;
-        P.pieces = P.oh <= kBsrTM ? 1 : (P.oh + kBsrTM - 1) / kBsrTM;
+        P.oh = oh, P.kb = trans ? bh : bw;
+        P.per_tile = split.per_tile, P.pieces = split.pieces;
         P.lanes = whole_lanes(vtype, {val, D}, {bw, ldd, p});
         return bsr_mm_dispatch<V>(itype, trans, P, s);
     });
@@ -77,7 +62,7 @@ int tsgu_bsr_mm_geometry(int vtype, int64_t bh, int64_t bw, int64_t p, int* tile
     if (p < 1 || bh < 1 || bw < 1) return TSGU_ERR_BAD_ARG;
     *tile_rows = kBsrTM;
     *tile_cols = vtype == TSGU_F64 ? bsr_tile_cols<double>(p) : bsr_tile_cols<float>(p);
-    *k_stage = vtype == TSGU_F32 ? ImmT<float>::KC : vtype == TSGU_F64 ? ImmT<double>::KC : ImmT<bf16_t>::KC;
+    *k_stage = vtype == TSGU_F32 ? MfmaT<float>::KC : vtype == TSGU_F64 ? MfmaT<double>::KC : MfmaT<bf16_t>::KC;
     return TSGU_OK;
 }
 

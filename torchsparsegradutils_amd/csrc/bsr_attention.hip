@@ -1,21 +1,13 @@
 // Block-sparse attention: the extern "C" entry points of include/tsgu_hip_bsr_attention.h (kernels: bsr_attention_impl.h, one
 // instantiation file per value type).
 #include "bsr_attention_impl.h"
+#include "bsr_host.h"
 
 #include "../../include/tsgu_hip_bsr_attention.h"
 
 using namespace tsgu;
 
 namespace {
-
-constexpr int64_t kI31 = 0x7fffffffLL;
-
-struct Dense {
-    const void* ptr;
-    int64_t ld;
-};
-
-int elem_bytes(int vtype) { return vtype == TSGU_F32 ? 4 : vtype == TSGU_F64 ? 8 : vtype == TSGU_BF16 ? 2 : 0; }
 
 bool geometry_ok(int heads, int d, int64_t bh, int64_t bw) {
     return heads >= 1 && (d == 16 || d == 32 || d == 64 || d == 128) && bh >= 16 && bw >= 16 && bh % 16 == 0 && bw % 16 == 0;
@@ -27,27 +19,19 @@ void geometry_of(int vtype, int d, int* tile_rows, int* stage_keys) {
     else bat_geometry<float>(d, tile_rows, stage_keys);
 }
 
-// The host-side refusals the three launchers share, in the order the header states.  `always`: pointers every call needs;
-// `stored`: those only a pattern with blocks dereferences (the gathered dense operands among them: null is allowed there).
+// The host-side refusals the three launchers share, in the order the header states (the gathered dense operands are among
+// `stored`: null is allowed there).
 int bat_check(int vtype, int itype, int64_t nrb, int64_t ncb, int64_t nnzb, int64_t bh, int64_t bw, int heads, int d,
               std::initializer_list<const void*> always, std::initializer_list<const void*> stored, std::initializer_list<Dense> dense) {
-    for (const void* q : always)
-        if (!q) return TSGU_ERR_BAD_ARG;
-    for (const void* q : stored)
-        if (!q && nnzb > 0) return TSGU_ERR_BAD_ARG;
-    const int eb = elem_bytes(vtype);
-    if (!eb || (itype != TSGU_I32 && itype != TSGU_I64)) return TSGU_ERR_BAD_DTYPE;
+    if (const int rc = bsr_check_args(vtype, itype, nnzb, always, stored)) return rc;
     if (nrb < 0 || ncb < 0 || nnzb < 0 || !geometry_ok(heads, d, bh, bw)) return TSGU_ERR_BAD_ARG;
     const int64_t width = (int64_t)heads * d;
     for (const Dense& o : dense) {
         if (!o.ptr) continue;
         if (o.ld < width) return TSGU_ERR_BAD_ARG;
-        if (!aligned16(o.ptr) || (o.ld * eb) % 16) return TSGU_ERR_BAD_ARG;      // rows are read in 16-byte lanes
+        if (!aligned16(o.ptr) || (o.ld * elem_bytes(vtype)) % 16) return TSGU_ERR_BAD_ARG;      // rows are read in 16-byte lanes
     }
-    for (const Dense& o : dense)
-        if (o.ptr && o.ld > 0xffffffffLL) return TSGU_ERR_TOO_LARGE;
-    if (bh > kI31 || bw > kI31 || nnzb > kI31 / bh / bw || nrb > kI31 / bh || ncb > kI31 / bw) return TSGU_ERR_TOO_LARGE;
-    return TSGU_OK;
+    return bsr_check_sizes(nrb, ncb, nnzb, bh, bw, dense, true);
 }
 
 struct Call {
@@ -65,15 +49,14 @@ int bat_run(const Call& c, int device, void* stream) {
     geometry_of(c.vtype, c.d, &T, &S);
     const bool cols = c.mode == kBatCols;
     const int64_t oh = cols ? c.bw : c.bh;
-    const int64_t per_tile = oh <= T ? T / oh : 1, pieces = oh <= T ? 1 : (oh + T - 1) / T;
-    const int64_t tiles = pieces > 1 ? c.n_groups * pieces : (c.n_groups + per_tile - 1) / per_tile;
+    const BsrSplit split = bsr_tile_split(oh, T, c.n_groups);
     const int heads_y = c.mode == kBatRows && c.dA ? 1 : c.heads;      // dA: the workgroup sums the heads itself
-    if (tiles > kI31 / heads_y) return TSGU_ERR_TOO_LARGE;
+    if (split.tiles > kI31 / heads_y) return TSGU_ERR_TOO_LARGE;
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return with_value_type<float, double, bf16_t>(c.vtype, [&](auto v) {
         using V = decltype(v);
-        using Acc = typename ImmT<V>::Part;
+        using Acc = typename MfmaT<V>::Part;
         BsrAttn<V> P{};
         P.ptr = c.ptr, P.idx = c.idx, P.perm = c.perm;
         P.val = static_cast<const V*>(c.bias);
@@ -84,11 +67,11 @@ int bat_run(const Call& c, int device, void* stream) {
         P.ldq = c.ldq, P.ldk = c.ldk, P.ldv = c.ldv, P.lddo = c.lddo, P.ldo = c.ldo, P.ld0 = c.ld0, P.ld1 = c.ld1;
         P.n_groups = c.n_groups, P.bh = c.bh, P.bw = c.bw;
         P.oh = oh, P.kb = cols ? c.bh : c.bw;
-        P.per_tile = per_tile, P.pieces = pieces;
+        P.per_tile = split.per_tile, P.pieces = split.pieces;
         P.heads = c.heads, P.heads_y = heads_y;
         P.i64 = c.itype == TSGU_I64;
         P.scale = (Acc)c.scale;
-        return bat_dispatch<V>(c.mode, c.d, P, tiles * heads_y, s);
+        return bat_dispatch<V>(c.mode, c.d, P, split.tiles * heads_y, s);
     });
 }
 

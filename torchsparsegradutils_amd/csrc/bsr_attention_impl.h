@@ -4,8 +4,9 @@
 // A workgroup owns T rows of the walked side and one head: T / oh whole block rows while the block height oh fits, else one piece
 // of one block row (the per_tile / pieces scheme of BsrMM, bsr_impl.h).  The block rows of a tile are walked one after the other;
 // the stored blocks of one are concatenated along the other side in stored order, S elements per LDS stage, so a wide block is
-// walked in pieces and narrow ones share a stage.  Every product is C[m][n] = sum_k X[m][k]·Y[n][k] on 16 x 16 MFMA tiles with the
-// lane maps of indexed_mm_impl.h; the four waves split n (the stage's elements for the logits, the d columns for the results).
+// walked in pieces and narrow ones share a stage.  Every product is C[m][n] = sum_k X[m][k]·Y[n][k] on 16 x 16 MFMA tiles: the lane
+// maps, the fragment loaders and the MFMA step are the matrix-core tile layer's (mfma_tile.h); the four waves split n (the stage's
+// elements for the logits, the d columns for the results).
 //
 //   forward      per stage: S = Q_tile·Kᵀ, + bias block, online softmax (running max m and sum l per row, kept in LDS; 256 / T
 //                lanes per row), P through LDS, O = O·exp(m_old − m_new) + P·V.  Writes O / l and lse = m + log l.
@@ -24,7 +25,7 @@
 // block row (block column); nothing waits for another workgroup.
 #pragma once
 
-#include "indexed_mm_impl.h"
+#include "mfma_tile.h"
 
 namespace tsgu {
 
@@ -44,7 +45,7 @@ constexpr int kBatMaxLds = 160 * 1024;
 
 template <typename V>
 struct BsrAttn {
-    using Acc = typename ImmT<V>::Part;
+    using Acc = typename MfmaT<V>::Part;
     const void* ptr;         // [n_groups + 1]: the walked side (block rows; block columns in the column pass)
     const void* idx;         // [nnzb]: block column (column pass: block row) of every walked block
     const void* perm;        // column pass: position of every walked block in val; NULL: identity
@@ -53,7 +54,7 @@ struct BsrAttn {
     const V* K;
     const V* Vv;
     const V* dO;
-    const typename ImmT<V>::Part* O;   // row pass: the forward's result before its rounding (its Oacc for bf16)
+    const typename MfmaT<V>::Part* O;   // row pass: the forward's result before its rounding (its Oacc for bf16)
     V* out0;                 // O, dQ, dK
     V* out1;                 // dV
     Acc* Oacc;               // forward, bf16: the result unrounded, [rows, heads·d] packed; NULL: not wanted
@@ -73,66 +74,9 @@ __device__ __forceinline__ int64_t bat_idx(const void* p, int64_t i, int i64) {
     return i64 ? static_cast<const int64_t*>(p)[i] : (int64_t) static_cast<const int32_t*>(p)[i];
 }
 
-template <typename V>
-constexpr int bat_pad() { return 16 / (int)sizeof(V); }
 // k extent of an image over the head width: the bf16 MFMA sums 32 elements, d = 16 is padded with zeros
 template <typename V, int D>
 constexpr int bat_dk() { return std::is_same<V, bf16_t>::value && D < 32 ? 32 : D; }
-
-template <typename V>
-struct BatFrag { using type = V; };
-template <>
-struct BatFrag<bf16_t> { using type = imm_bf16x8; };
-
-// MFMA operand of lane (r, q) from an image with k contiguous: T[row][k0 ..]
-template <typename V, int P>
-__device__ __forceinline__ typename BatFrag<V>::type frag_k(const V* T, int row, int k0, int q) {
-    if constexpr (std::is_same<V, bf16_t>::value) return *reinterpret_cast<const imm_bf16x8*>(T + row * P + k0 + 8 * q);
-    else return T[row * P + k0 + q];
-}
-// ... and from an image stored the other way round: T[k][row]
-template <typename V, int P>
-__device__ __forceinline__ typename BatFrag<V>::type frag_t(const V* T, int row, int k0, int q) {
-    if constexpr (std::is_same<V, bf16_t>::value) {
-        uint16_t w[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) w[j] = T[(k0 + 8 * q + j) * P + row].bits;
-        imm_bf16x8 f;
-        __builtin_memcpy(&f, w, 16);
-        return f;
-    } else {
-        return T[(k0 + q) * P + row];
-    }
-}
-
-template <typename V>
-__device__ __forceinline__ typename ImmT<V>::Acc bat_mfma(typename BatFrag<V>::type a, typename BatFrag<V>::type b,
-                                                          typename ImmT<V>::Acc c) {
-    if constexpr (std::is_same<V, bf16_t>::value) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    else if constexpr (std::is_same<V, double>::value) return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// acc[mt][nt] += X(mt, k0) · Y(nt, k0)ᵀ over k0 in [0, k_end), for the row tiles [m_lo, m_hi) and the first n_cnt column tiles
-// (all uniform over the wave).
-template <typename V, int MT, int NT, typename FX, typename FY>
-__device__ __forceinline__ void bat_mma(typename ImmT<V>::Acc (&acc)[MT][NT], int m_lo, int m_hi, int n_cnt, int k_end, FX fx, FY fy) {
-    constexpr int KS = ImmT<V>::KS;
-    for (int k0 = 0; k0 < k_end; k0 += KS) {
-        typename BatFrag<V>::type yb[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            if (nt < n_cnt) yb[nt] = fy(nt, k0);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            if (mt < m_lo || mt >= m_hi) continue;
-            const typename BatFrag<V>::type xa = fx(mt, k0);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                if (nt < n_cnt) acc[mt][nt] = bat_mfma<V>(xa, yb[nt], acc[mt][nt]);
-        }
-    }
-}
 
 // Img[i][0 .. DK) (pitch P) = src[row(i)·ld + c], c < D, zero for row(i) < 0 and for the padding c >= D; 16-byte lanes throughout.
 template <typename V, int ROWS, int D, int DK, int P, typename Row>
@@ -214,9 +158,9 @@ __device__ __forceinline__ void bat_stage_index(const BsrAttn<V>& p, int64_t e_l
 
 template <typename V, int D>
 struct BatLds {
-    using Acc = typename ImmT<V>::Part;
+    using Acc = typename MfmaT<V>::Part;
     static constexpr int T = BatG<V, D>::T, S = BatG<V, D>::S;
-    static constexpr int DK = bat_dk<V, D>(), PD = DK + bat_pad<V>(), PS = S + bat_pad<V>(), PL = S + 1;
+    static constexpr int DK = bat_dk<V, D>(), PD = DK + lds_pad<V>(), PS = S + lds_pad<V>(), PL = S + 1;
     static constexpr int up16(int b) { return (b + 15) / 16 * 16; }
     static constexpr int kIndex = 2 * S * 8;
     static constexpr int kOwn = up16(T * PD * (int)sizeof(V)), kFar = up16(S * PD * (int)sizeof(V));
@@ -227,14 +171,14 @@ struct BatLds {
     static constexpr int kRows = kIndex + up16(2 * T * (int)sizeof(Acc)) + 2 * kOwn + 2 * kFar + kP;
     static constexpr int kCols = kIndex + up16(2 * S * (int)sizeof(Acc)) + 2 * kOwn + 2 * kFar + 2 * kP + kSplit / 2;
     static_assert(kFwd <= kBatMaxLds && kRows <= kBatMaxLds && kCols <= kBatMaxLds, "the LDS images must fit one CU");
-    static_assert(S % ImmT<V>::KS == 0 && DK % ImmT<V>::KS == 0 && S % 16 == 0 && kBlock % T == 0, "whole MFMA steps");
+    static_assert(S % MfmaT<V>::KS == 0 && DK % MfmaT<V>::KS == 0 && S % 16 == 0 && kBlock % T == 0, "whole MFMA steps");
 };
 
 template <typename V, int D>
 __global__ void __launch_bounds__(kBlock) bat_fwd_kernel(BsrAttn<V> p) {
     using L = BatLds<V, D>;
-    using Acc = typename ImmT<V>::Part;
-    using AccV = typename ImmT<V>::Acc;
+    using Acc = typename MfmaT<V>::Part;
+    using AccV = typename MfmaT<V>::Acc;
     constexpr int T = L::T, S = L::S, MT = T / 16, DK = L::DK, PD = L::PD, PS = L::PS, PL = L::PL;
     constexpr int NT_S = (S / 16 + 3) / 4, NT_O = (D / 16 + 3) / 4, TPR = kBlock / T;
     extern __shared__ __attribute__((aligned(16))) unsigned char bat_smem[];
@@ -300,8 +244,8 @@ __global__ void __launch_bounds__(kBlock) bat_fwd_kernel(BsrAttn<V> p) {
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                     for (int nt = 0; nt < NT_S; ++nt) s[mt][nt] = AccV{};
-                bat_mma<V, MT, NT_S>(s, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Qs, 16 * mt + r, k, q); },
-                                     [&](int nt, int k) { return frag_k<V, PD>(Ks, nbs + 16 * nt + r, k, q); });
+                mfma_step<V, MT, NT_S>(s, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Qs, 16 * mt + r, k, q); },
+                                       [&](int nt, int k) { return frag_k<V, PD>(Ks, nbs + 16 * nt + r, k, q); });
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     if (mt < m_lo || mt >= m_hi) continue;
@@ -373,14 +317,14 @@ __global__ void __launch_bounds__(kBlock) bat_fwd_kernel(BsrAttn<V> p) {
                     }
                 }
             }
-            bat_mma<V, MT, NT_O>(acc, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Ps, 16 * mt + r, k, q); },
-                                 [&](int nt, int k) { return frag_k<V, PS>(Vt, nbo + 16 * nt + r, k, q); });
+            mfma_step<V, MT, NT_O>(acc, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Ps, 16 * mt + r, k, q); },
+                                   [&](int nt, int k) { return frag_k<V, PS>(Vt, nbo + 16 * nt + r, k, q); });
             if constexpr (kCanSplit) {
-                bat_mma<V, MT, NT_O>(acc, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pm, 16 * mt + r, k, q); },
-                                     [&](int nt, int k) { return frag_k<V, PS>(Vt, nbo + 16 * nt + r, k, q); });
+                mfma_step<V, MT, NT_O>(acc, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pm, 16 * mt + r, k, q); },
+                                       [&](int nt, int k) { return frag_k<V, PS>(Vt, nbo + 16 * nt + r, k, q); });
                 if (split)
-                    bat_mma<V, MT, NT_O>(rest, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pl, 16 * mt + r, k, q); },
-                                         [&](int nt, int k) { return frag_k<V, PS>(Vt, nbo + 16 * nt + r, k, q); });
+                    mfma_step<V, MT, NT_O>(rest, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pl, 16 * mt + r, k, q); },
+                                           [&](int nt, int k) { return frag_k<V, PS>(Vt, nbo + 16 * nt + r, k, q); });
             }
             __syncthreads();
         }
@@ -420,8 +364,8 @@ __global__ void __launch_bounds__(kBlock) bat_fwd_kernel(BsrAttn<V> p) {
 template <typename V, int D>
 __global__ void __launch_bounds__(kBlock) bat_rows_kernel(BsrAttn<V> p) {
     using L = BatLds<V, D>;
-    using Acc = typename ImmT<V>::Part;
-    using AccV = typename ImmT<V>::Acc;
+    using Acc = typename MfmaT<V>::Part;
+    using AccV = typename MfmaT<V>::Acc;
     constexpr int T = L::T, S = L::S, MT = T / 16, DK = L::DK, PD = L::PD, PS = L::PS;
     constexpr int NT_S = (S / 16 + 3) / 4, NT_O = (D / 16 + 3) / 4, TPR = kBlock / T;
     extern __shared__ __attribute__((aligned(16))) unsigned char bat_smem[];
@@ -497,10 +441,10 @@ __global__ void __launch_bounds__(kBlock) bat_rows_kernel(BsrAttn<V> p) {
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                         for (int nt = 0; nt < NT_S; ++nt) s[mt][nt] = dp[mt][nt] = AccV{};
-                    bat_mma<V, MT, NT_S>(s, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Qs, 16 * mt + r, k, q); },
-                                         [&](int nt, int k) { return frag_k<V, PD>(Ks, nbs + 16 * nt + r, k, q); });
-                    bat_mma<V, MT, NT_S>(dp, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Gs, 16 * mt + r, k, q); },
-                                         [&](int nt, int k) { return frag_k<V, PD>(Vs, nbs + 16 * nt + r, k, q); });
+                    mfma_step<V, MT, NT_S>(s, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Qs, 16 * mt + r, k, q); },
+                                           [&](int nt, int k) { return frag_k<V, PD>(Ks, nbs + 16 * nt + r, k, q); });
+                    mfma_step<V, MT, NT_S>(dp, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Gs, 16 * mt + r, k, q); },
+                                           [&](int nt, int k) { return frag_k<V, PD>(Vs, nbs + 16 * nt + r, k, q); });
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt) {
                         if (mt < m_lo || mt >= m_hi) continue;
@@ -527,8 +471,8 @@ __global__ void __launch_bounds__(kBlock) bat_rows_kernel(BsrAttn<V> p) {
                     }
                 }
                 __syncthreads();
-                bat_mma<V, MT, NT_O>(acc, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Ps, 16 * mt + r, k, q); },
-                                     [&](int nt, int k) { return frag_t<V, PD>(Ks, nbo + 16 * nt + r, k, q); });
+                mfma_step<V, MT, NT_O>(acc, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Ps, 16 * mt + r, k, q); },
+                                       [&](int nt, int k) { return frag_t<V, PD>(Ks, nbo + 16 * nt + r, k, q); });
                 __syncthreads();
             }
         }
@@ -551,8 +495,8 @@ __global__ void __launch_bounds__(kBlock) bat_rows_kernel(BsrAttn<V> p) {
 template <typename V, int D>
 __global__ void __launch_bounds__(kBlock) bat_cols_kernel(BsrAttn<V> p) {
     using L = BatLds<V, D>;
-    using Acc = typename ImmT<V>::Part;
-    using AccV = typename ImmT<V>::Acc;
+    using Acc = typename MfmaT<V>::Part;
+    using AccV = typename MfmaT<V>::Acc;
     constexpr int T = L::T, S = L::S, MT = T / 16, DK = L::DK, PD = L::PD, PS = L::PS;
     constexpr int NT_S = (S / 16 + 3) / 4, NT_O = (D / 16 + 3) / 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char bat_smem[];
@@ -620,10 +564,10 @@ __global__ void __launch_bounds__(kBlock) bat_cols_kernel(BsrAttn<V> p) {
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                     for (int nt = 0; nt < NT_S; ++nt) s[mt][nt] = dp[mt][nt] = AccV{};
-                bat_mma<V, MT, NT_S>(s, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Ks, 16 * mt + r, k, q); },
-                                     [&](int nt, int k) { return frag_k<V, PD>(Qf, nbs + 16 * nt + r, k, q); });
-                bat_mma<V, MT, NT_S>(dp, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Vs, 16 * mt + r, k, q); },
-                                     [&](int nt, int k) { return frag_k<V, PD>(Gf, nbs + 16 * nt + r, k, q); });
+                mfma_step<V, MT, NT_S>(s, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Ks, 16 * mt + r, k, q); },
+                                       [&](int nt, int k) { return frag_k<V, PD>(Qf, nbs + 16 * nt + r, k, q); });
+                mfma_step<V, MT, NT_S>(dp, m_lo, m_hi, ns_cnt, DK, [&](int mt, int k) { return frag_k<V, PD>(Vs, 16 * mt + r, k, q); },
+                                       [&](int nt, int k) { return frag_k<V, PD>(Gf, nbs + 16 * nt + r, k, q); });
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     if (mt < m_lo || mt >= m_hi) continue;
@@ -651,13 +595,13 @@ __global__ void __launch_bounds__(kBlock) bat_cols_kernel(BsrAttn<V> p) {
                 }
             }
             __syncthreads();
-            bat_mma<V, MT, NT_O>(dv, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pt, 16 * mt + r, k, q); },
-                                 [&](int nt, int k) { return frag_t<V, PD>(Gf, nbo + 16 * nt + r, k, q); });
+            mfma_step<V, MT, NT_O>(dv, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pt, 16 * mt + r, k, q); },
+                                   [&](int nt, int k) { return frag_t<V, PD>(Gf, nbo + 16 * nt + r, k, q); });
             if constexpr (kCanSplit)
-                bat_mma<V, MT, NT_O>(dv, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pm, 16 * mt + r, k, q); },
-                                     [&](int nt, int k) { return frag_t<V, PD>(Gf, nbo + 16 * nt + r, k, q); });
-            bat_mma<V, MT, NT_O>(dk, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(St, 16 * mt + r, k, q); },
-                                 [&](int nt, int k) { return frag_t<V, PD>(Qf, nbo + 16 * nt + r, k, q); });
+                mfma_step<V, MT, NT_O>(dv, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(Pm, 16 * mt + r, k, q); },
+                                       [&](int nt, int k) { return frag_t<V, PD>(Gf, nbo + 16 * nt + r, k, q); });
+            mfma_step<V, MT, NT_O>(dk, m_lo, m_hi, no_cnt, S, [&](int mt, int k) { return frag_k<V, PS>(St, 16 * mt + r, k, q); },
+                                   [&](int nt, int k) { return frag_t<V, PD>(Qf, nbo + 16 * nt + r, k, q); });
             __syncthreads();
         }
     }

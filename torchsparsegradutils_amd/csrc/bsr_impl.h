@@ -1,7 +1,7 @@
 // Block-sparse (BSR) × dense products on the matrix cores: sparse_bsr_mm's forward, its transposed product and the block SDDMM.
 //
-// The LDS images, their padding (one 16-byte pad per row), the MFMA lane maps and the k-major / row-major staging are those of
-// indexed_mm_impl.h (included for them).  Every product is C[m][n] = sum_k X[m][k] * Y[n][k]:
+// The LDS images, their padding (one 16-byte pad per row), the MFMA lane maps and the k-major / row-major staging are the
+// matrix-core tile layer's (mfma_tile.h).  Every product is C[m][n] = sum_k X[m][k] * Y[n][k]:
 //   forward     X = the stored blocks' rows (k along bw, contiguous in memory), Y = the slab of B the block column names (n contiguous)
 //   transposed  X = V[perm]ᵀ (m along bw, contiguous in memory; k along bh),   Y = the slab of G the block row names
 //   SDDMM       X = rows of G, Y = rows of B, both with k = the dense column contiguous; one block (or one 64 x 64 piece of it)
@@ -13,7 +13,7 @@
 // A workgroup's work follows from its grid index alone; nothing waits for another workgroup.
 #pragma once
 
-#include "indexed_mm_impl.h"
+#include "mfma_tile.h"
 
 namespace tsgu {
 
@@ -26,38 +26,20 @@ constexpr int bsr_tile_cols(int64_t p) { return !std::is_same<V, double>::value 
 // acc[mt][nt] += X[16 mt .. +16][0 .. k_end) · Y[nb + 16 nt .. +16][0 .. k_end)ᵀ for the row tiles mt in [m_lo, m_hi) (uniform).
 template <typename V, int NT, int P>
 __device__ __forceinline__ void bsr_mfma(const V* X, const V* Y, int nb, int m_lo, int m_hi, int k_end,
-                                         typename ImmT<V>::Acc (&acc)[kBsrMT][NT]) {
-    constexpr int KS = ImmT<V>::KS;
+                                         typename MfmaT<V>::Acc (&acc)[kBsrMT][NT]) {
+    constexpr int KS = MfmaT<V>::KS;
     const int lane = threadIdx.x & (kWave - 1);
     const int r = lane & 15, q = lane >> 4;
     for (int k0 = 0; k0 < k_end; k0 += KS) {
-        if constexpr (std::is_same<V, bf16_t>::value) {
-            imm_bf16x8 yb[NT];
+        typename MfmaT<V>::Frag yb[NT];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) yb[nt] = *reinterpret_cast<const imm_bf16x8*>(Y + (nb + 16 * nt + r) * P + k0 + 8 * q);
+        for (int nt = 0; nt < NT; ++nt) yb[nt] = frag_k<V, P>(Y, nb + 16 * nt + r, k0, q);
 #pragma unroll
-            for (int mt = 0; mt < kBsrMT; ++mt) {
-                if (mt < m_lo || mt >= m_hi) continue;
-                const imm_bf16x8 xa = *reinterpret_cast<const imm_bf16x8*>(X + (16 * mt + r) * P + k0 + 8 * q);
+        for (int mt = 0; mt < kBsrMT; ++mt) {
+            if (mt < m_lo || mt >= m_hi) continue;
+            const typename MfmaT<V>::Frag xa = frag_k<V, P>(X, 16 * mt + r, k0, q);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa, yb[nt], acc[mt][nt], 0, 0, 0);
-            }
-        } else {
-            V yb[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) yb[nt] = Y[(nb + 16 * nt + r) * P + k0 + q];
-#pragma unroll
-            for (int mt = 0; mt < kBsrMT; ++mt) {
-                if (mt < m_lo || mt >= m_hi) continue;
-                const V xa = X[(16 * mt + r) * P + k0 + q];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    if constexpr (std::is_same<V, double>::value)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, yb[nt], acc[mt][nt], 0, 0, 0);
-                    else
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa, yb[nt], acc[mt][nt], 0, 0, 0);
-                }
-            }
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma_16x16<V>(xa, yb[nt], acc[mt][nt]);
         }
     }
 }
@@ -226,7 +208,7 @@ __device__ __forceinline__ void bsr_stage_rows_lanes(V* Xs, V* Ys, const V* __re
 
 template <typename V, typename I, int BN, bool TRANS>
 __global__ void __launch_bounds__(kBlock) bsr_mm_kernel(BsrMM<V> p) {
-    constexpr int KC = ImmT<V>::KC, KS = ImmT<V>::KS, P = imm_pitch<V>();
+    constexpr int KC = MfmaT<V>::KC, KS = MfmaT<V>::KS, P = mfma_pitch<V>();
     constexpr int NT = BN / 16 / (kBlock / kWave);
     __shared__ __attribute__((aligned(16))) V Xs[kBsrTM * P];
     __shared__ __attribute__((aligned(16))) V Ys[BN * P];
@@ -244,11 +226,11 @@ __global__ void __launch_bounds__(kBlock) bsr_mm_kernel(BsrMM<V> p) {
 
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int nb = wave * NT * 16;
-    typename ImmT<V>::Acc acc[kBsrMT][NT];
+    typename MfmaT<V>::Acc acc[kBsrMT][NT];
 #pragma unroll
     for (int mt = 0; mt < kBsrMT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename ImmT<V>::Acc{};
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename MfmaT<V>::Acc{};
 
     for (int64_t g = g_lo; g < g_hi; ++g) {
         const int a_lo = (int)(g - g_lo) * rows_each, a_hi = a_lo + rows_each;
@@ -323,7 +305,7 @@ struct BsrSddmm {
 // The blocks of a block row read the same rows of G: they are neighbours in the grid, and the rows come from L2.
 template <typename V, typename I>
 __global__ void __launch_bounds__(kBlock) bsr_sddmm_kernel(BsrSddmm<V> p) {
-    constexpr int KC = ImmT<V>::KC, KS = ImmT<V>::KS, P = imm_pitch<V>();
+    constexpr int KC = MfmaT<V>::KC, KS = MfmaT<V>::KS, P = mfma_pitch<V>();
     __shared__ __attribute__((aligned(16))) V Xs[kBsrTM * P];
     __shared__ __attribute__((aligned(16))) V Ys[kBsrTM * P];
 
@@ -336,9 +318,9 @@ __global__ void __launch_bounds__(kBlock) bsr_sddmm_kernel(BsrSddmm<V> p) {
 
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int nb = wave * 16;
-    typename ImmT<V>::Acc acc[kBsrMT][1];
+    typename MfmaT<V>::Acc acc[kBsrMT][1];
 #pragma unroll
-    for (int mt = 0; mt < kBsrMT; ++mt) acc[mt][0] = typename ImmT<V>::Acc{};
+    for (int mt = 0; mt < kBsrMT; ++mt) acc[mt][0] = typename MfmaT<V>::Acc{};
 
     for (int64_t k0 = 0; k0 < p.p; k0 += KC) {
         const int k_ok = (int)min((int64_t)KC, p.p - k0);

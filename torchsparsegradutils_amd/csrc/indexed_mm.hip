@@ -50,7 +50,7 @@ ImmGradB<V> gradb_params(const void* offsets, const void* chunk_ptr, const void*
     P.a = static_cast<const V*>(a);
     P.g = static_cast<const V*>(g);
     P.gb = static_cast<V*>(grad_b);
-    P.part = static_cast<typename ImmT<V>::Part*>(ws);
+    P.part = static_cast<typename MfmaT<V>::Part*>(ws);
     P.lda = lda;
     P.ldg = ldg;
     P.n_seg = n_seg;

@@ -8,171 +8,36 @@
 // A workgroup finds its (segment, tile) by a binary search over tile_ptr, so the grid needs no host read-back: it is launched
 // with a bound (ceil(n / BM) + min(n_seg, n) + 2 >= tile_ptr[n_seg + 2]) and the workgroups beyond the last tile exit.
 //
-// Every product is C[m][n] = sum_k X[m][k] * Y[n][k] over two LDS images with k contiguous: X = a's row tile (forward) or aᵀ
-// (grad_b), Y = b[r]ᵀ (forward) or gᵀ (grad_b).  MFMA lane maps (cdna_hip_programming.md §3):
-//   f32  16x16x4f32:  lane l holds X[l&15][k0 + (l>>4)] and Y[l&15][k0 + (l>>4)];  C: col = l&15, row = 4*(l>>4) + reg
-//   f64  16x16x4f64:  A/B as f32;                                                 C: col = l&15, row = (l>>4) + 4*reg
-//   bf16 16x16x32:    lane l holds X[l&15][k0 + 8(l>>4) + j], j < 8 (and Y alike); C as f32
-// The f32 form is bit for bit a k-ordered fmaf chain; the bf16 form multiplies exactly and accumulates in fp32.  Zero padding
-// past D1 / D2 / the segment end adds exact zeros.
+// The LDS images, their padding, the MFMA lane maps and the staging are the matrix-core tile layer's (mfma_tile.h): X = a's row
+// tile (forward) or aᵀ (grad_b), Y = b[r]ᵀ (forward) or gᵀ (grad_b), both with k contiguous.  Zero padding past D1 / D2 / the
+// segment end adds exact zeros.
 #pragma once
 
-#include "tsgu_common.h"
+#include "mfma_tile.h"
 
 namespace tsgu {
 
 constexpr int kImmBM = 128;                    // rows of one forward tile
 constexpr int kImmGT = 64;                     // grad_b output tile: kImmGT x kImmGT of (D1, D2)
 
-typedef __bf16 imm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float imm_f32x4 __attribute__((ext_vector_type(4)));
-typedef double imm_f64x4 __attribute__((ext_vector_type(4)));
-
-template <typename V>
-struct ImmT;
-template <>
-struct ImmT<float> {
-    static constexpr int KC = 64;              // k per LDS stage
-    static constexpr int KS = 4;               // k per MFMA
-    using Acc = imm_f32x4;
-    using Part = float;
-};
-template <>
-struct ImmT<double> {
-    static constexpr int KC = 32;
-    static constexpr int KS = 4;
-    using Acc = imm_f64x4;
-    using Part = double;
-};
-template <>
-struct ImmT<bf16_t> {
-    static constexpr int KC = 128;
-    static constexpr int KS = 32;
-    using Acc = imm_f32x4;
-    using Part = float;
-};
-
-template <typename V>
-constexpr int imm_pitch() { return ImmT<V>::KC + 16 / (int)sizeof(V); }   // one 16-byte pad per LDS row
-
-template <typename I>
-__device__ __forceinline__ int64_t ld_idx(const void* p, int64_t i) { return (int64_t) static_cast<const I*>(p)[i]; }
-
-// Largest e in [0, n) with ptr[e] <= t (ptr ascending, ptr[0] = 0 <= t).
-template <typename I>
-__device__ __forceinline__ int64_t upper_slot(const void* ptr, int64_t n, int64_t t) {
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (ld_idx<I>(ptr, mid) <= t) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// T[row][k] (pitch P) = src[base(row) + k] for row < ROWS, k < KC; zero where row >= rows_ok, k >= k_ok or base(row) < 0.
-// k is contiguous in memory: 16-byte loads and 16-byte LDS writes where the address allows.
-template <typename V, int ROWS, int KC, int P, typename Base>
-__device__ __forceinline__ void stage_kmajor(V* T, const V* __restrict__ src, int rows_ok, int k_ok, Base base) {
-    constexpr int W = VT<V>::kWide;
-    constexpr int PER_ROW = KC / W;
-    for (int v = threadIdx.x; v < ROWS * PER_ROW; v += kBlock) {
-        const int row = v / PER_ROW, k = (v % PER_ROW) * W;
-        V* dst = T + row * P + k;
-        const int64_t off = row < rows_ok ? base(row) : -1;
-        if (off < 0 || k >= k_ok) {
-            *reinterpret_cast<uint4*>(dst) = make_uint4(0, 0, 0, 0);
-            continue;
-        }
-        const V* s = src + off + k;
-        if (k + W <= k_ok && al16(s)) {
-            *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(s);
-        } else {
-            V tmp[W];
-#pragma unroll
-            for (int j = 0; j < W; ++j) tmp[j] = k + j < k_ok ? s[j] : V{};
-            __builtin_memcpy(dst, tmp, 16);
-        }
-    }
-}
-
-// T[row][k] (pitch P) = src[base(k) + row]: the row index is contiguous in memory (16-byte loads, scattered LDS writes).
-template <typename V, int ROWS, int KC, int P, typename Base>
-__device__ __forceinline__ void stage_rmajor(V* T, const V* __restrict__ src, int rows_ok, int k_ok, Base base) {
-    constexpr int W = VT<V>::kWide;
-    constexpr int PER_K = ROWS / W;
-    for (int v = threadIdx.x; v < KC * PER_K; v += kBlock) {
-        const int k = v / PER_K, row = (v % PER_K) * W;
-        const int64_t off = k < k_ok ? base(k) : -1;
-        V tmp[W];
-        if (off < 0 || row >= rows_ok) {
-#pragma unroll
-            for (int j = 0; j < W; ++j) tmp[j] = V{};
-        } else {
-            const V* s = src + off + row;
-            if (row + W <= rows_ok && al16(s)) {
-                const uint4 raw = *reinterpret_cast<const uint4*>(s);
-                __builtin_memcpy(tmp, &raw, 16);
-            } else {
-#pragma unroll
-                for (int j = 0; j < W; ++j) tmp[j] = row + j < rows_ok ? s[j] : V{};
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < W; ++j) T[(row + j) * P + k] = tmp[j];
-    }
-}
-
 // acc[mt][nt] += X[mb + 16 mt .. +16][0 .. KC) · Y[16 nt .. +16][0 .. KC)ᵀ for one wave.
 template <typename V, int MT, int NT, int P>
-__device__ __forceinline__ void mfma_stage(const V* X, const V* Y, int mb, typename ImmT<V>::Acc (&acc)[MT][NT]) {
-    constexpr int KC = ImmT<V>::KC, KS = ImmT<V>::KS;
+__device__ __forceinline__ void mfma_stage(const V* X, const V* Y, int mb, typename MfmaT<V>::Acc (&acc)[MT][NT]) {
+    constexpr int KC = MfmaT<V>::KC, KS = MfmaT<V>::KS;
     const int lane = threadIdx.x & (kWave - 1);
     const int r = lane & 15, q = lane >> 4;
 #pragma unroll 2
     for (int k0 = 0; k0 < KC; k0 += KS) {
-        if constexpr (std::is_same<V, bf16_t>::value) {
-            imm_bf16x8 xa[MT], yb[NT];
+        typename MfmaT<V>::Frag xa[MT], yb[NT];
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) xa[mt] = *reinterpret_cast<const imm_bf16x8*>(X + (mb + 16 * mt + r) * P + k0 + 8 * q);
+        for (int mt = 0; mt < MT; ++mt) xa[mt] = frag_k<V, P>(X, mb + 16 * mt + r, k0, q);
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) yb[nt] = *reinterpret_cast<const imm_bf16x8*>(Y + (16 * nt + r) * P + k0 + 8 * q);
+        for (int nt = 0; nt < NT; ++nt) yb[nt] = frag_k<V, P>(Y, 16 * nt + r, k0, q);
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
+        for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[mt], yb[nt], acc[mt][nt], 0, 0, 0);
-        } else {
-            V xa[MT], yb[NT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) xa[mt] = X[(mb + 16 * mt + r) * P + k0 + q];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) yb[nt] = Y[(16 * nt + r) * P + k0 + q];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    if constexpr (std::is_same<V, double>::value)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[mt], yb[nt], acc[mt][nt], 0, 0, 0);
-                    else
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[mt], yb[nt], acc[mt][nt], 0, 0, 0);
-                }
-        }
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma_16x16<V>(xa[mt], yb[nt], acc[mt][nt]);
     }
-}
-
-// (row, column) inside a 16 x 16 MFMA result of accumulator register `reg` on lane `lane`.
-template <typename V>
-__device__ __forceinline__ int acc_row(int lane, int reg) {
-    if constexpr (std::is_same<V, double>::value) return (lane >> 4) + 4 * reg;
-    else return 4 * (lane >> 4) + reg;
-}
-
-template <typename V>
-__device__ __forceinline__ V to_v(typename ImmT<V>::Part x) {
-    if constexpr (std::is_same<V, bf16_t>::value) return VT<bf16_t>::down(x);
-    else return x;
 }
 
 template <typename V>
@@ -190,7 +55,7 @@ struct ImmFwd {
 // out[perm[i]] = a[perm[i]] @ b[r] for the rows i of one row tile of segment r, columns [n0, n0 + BN).
 template <typename V, typename I, int BN>
 __global__ void __launch_bounds__(kBlock) imm_fwd_kernel(ImmFwd<V> p) {
-    constexpr int KC = ImmT<V>::KC, P = imm_pitch<V>();
+    constexpr int KC = MfmaT<V>::KC, P = mfma_pitch<V>();
     constexpr int MT = kImmBM / 16 / (kBlock / kWave), NT = BN / 16;
     __shared__ __attribute__((aligned(16))) V Xs[kImmBM * P];
     __shared__ __attribute__((aligned(16))) V Ys[BN * P];
@@ -213,11 +78,11 @@ __global__ void __launch_bounds__(kBlock) imm_fwd_kernel(ImmFwd<V> p) {
 
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int mb = wave * MT * 16;
-    typename ImmT<V>::Acc acc[MT][NT];
+    typename MfmaT<V>::Acc acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename ImmT<V>::Acc{};
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename MfmaT<V>::Acc{};
 
     if (live) {
         const int64_t bro = (e - 1) * p.bs0;
@@ -259,7 +124,7 @@ struct ImmGradB {
     const V* a;              // (n, d1), rows through perm
     const V* g;              // (n, d2), rows through perm
     V* gb;                   // (n_seg, d1, d2) contiguous
-    typename ImmT<V>::Part* part;   // partial slots of d1 * d2 each
+    typename MfmaT<V>::Part* part;   // partial slots of d1 * d2 each
     int64_t lda, ldg;
     int64_t n_seg, d1, d2, chunk;
 };
@@ -268,7 +133,7 @@ struct ImmGradB {
 // chunk, else into its partial slot.  Rows are taken in order, KC at a time, each product an ordered fmaf chain (f32, f64).
 template <typename V, typename I>
 __global__ void __launch_bounds__(kBlock) imm_gradb_kernel(ImmGradB<V> p) {
-    constexpr int KC = ImmT<V>::KC, P = imm_pitch<V>();
+    constexpr int KC = MfmaT<V>::KC, P = mfma_pitch<V>();
     constexpr int MT = kImmGT / 16 / (kBlock / kWave), NT = kImmGT / 16;
     __shared__ __attribute__((aligned(16))) V Xs[kImmGT * P];
     __shared__ __attribute__((aligned(16))) V Ys[kImmGT * P];
@@ -287,11 +152,11 @@ __global__ void __launch_bounds__(kBlock) imm_gradb_kernel(ImmGradB<V> p) {
 
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int mb = wave * MT * 16;
-    typename ImmT<V>::Acc acc[MT][NT];
+    typename MfmaT<V>::Acc acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename ImmT<V>::Acc{};
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = typename MfmaT<V>::Acc{};
 
     for (int64_t k0 = lo; k0 < hi; k0 += KC) {
         const int k_ok = (int)min((int64_t)KC, hi - k0);
@@ -306,7 +171,7 @@ __global__ void __launch_bounds__(kBlock) imm_gradb_kernel(ImmGradB<V> p) {
     }
 
     const bool direct = nch == 1;
-    using Part = typename ImmT<V>::Part;
+    using Part = typename MfmaT<V>::Part;
     Part* slot = direct ? nullptr : p.part + (ld_idx<I>(p.part_ptr, r) + c) * p.d1 * p.d2;
     V* dst = p.gb + r * p.d1 * p.d2;
 #pragma unroll
@@ -335,7 +200,7 @@ __global__ void __launch_bounds__(kBlock) imm_gradb_reduce_kernel(ImmGradB<V> p)
     const int64_t per = p.d1 * p.d2;
     const int64_t at = (int64_t)blockIdx.y * kBlock + threadIdx.x;
     if (at >= per) return;
-    using Part = typename ImmT<V>::Part;
+    using Part = typename MfmaT<V>::Part;
     Part s = 0;
     const Part* src = p.part + ld_idx<I>(p.part_ptr, r) * per + at;
     for (int64_t c = 0; c < nch; ++c) s += src[c * per];
