@@ -226,6 +226,15 @@ SIGNATURES_BSR_ATTENTION = {
                _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _i64, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_factor.h (same library, same ABI version)
+_FACTOR_ARGS = [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _dbl, _ptr, _ptr, _ptr, _int, _int, _ptr]
+SIGNATURES_FACTOR = {
+    "tsgu_csr_factor_work_bytes": (_i64, [_i64]),
+    "tsgu_csr_factor_geometry": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_ilu0": (_int, list(_FACTOR_ARGS)),
+    "tsgu_csr_ic0": (_int, list(_FACTOR_ARGS)),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -250,7 +259,7 @@ def load_library():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
                                   *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items(), *SIGNATURES_BSR.items(),
-                                  *SIGNATURES_BSR_ATTENTION.items()):
+                                  *SIGNATURES_BSR_ATTENTION.items(), *SIGNATURES_FACTOR.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -1345,6 +1354,47 @@ def csr_sptrsm_lattice(tables, val, B, n: int, lower: bool, unit: bool, workgrou
            X, _ld(X), p, work, int(workgroups))
     _defer_error_check(work[512:516].view(torch.int32), dev, "tsgu_csr_sptrsm_lattice (dependency wait)")
     return X
+
+
+FACTOR_DTYPES = (torch.float32, torch.float64)
+
+
+def factor_geometry(dtype: torch.dtype):
+    """(row_capacity, waves_per_block) of the incomplete factorisations for `dtype`: the entries of a row that are staged in LDS (a
+    longer row is built in the output array itself) and the rows a workgroup has in flight."""
+    cap, waves = _int(0), _int(0)
+    check(load_library().tsgu_csr_factor_geometry(_VTYPE[dtype], ctypes.byref(cap), ctypes.byref(waves)), "tsgu_csr_factor_geometry")
+    return cap.value, waves.value
+
+
+def csr_factor(kind: str, ptr, idx, diag_pos, val, n: int, shift: float = 0.0, wg_per_cu: int = 1, out=None):
+    """The zero-fill incomplete factor of the CSR matrix (ptr, idx, val) on its own pattern (include/tsgu_hip_factor.h): `kind`
+    "ilu0" (combined L \\ U array) or "ic0" (the arrays are those of tril(A)).  Columns ascending and unique per row, every diagonal
+    stored, `diag_pos` its position per row — the caller's plan has checked that.  Returns (out, info): `info` a device int64, 0 or
+    1 + the lowest row that broke down; nothing is read back here but the error word of the bounded waits, by the protocol of
+    `csr_sptrsm`.  `out` may be `val` itself."""
+    if kind not in ("ilu0", "ic0"):
+        raise ValueError(f"csr_factor: unknown factorisation {kind!r}")
+    if val.dtype not in FACTOR_DTYPES:
+        raise TypeError(f"tsgu_csr_{kind}: float32 and float64 values only, got {val.dtype}")
+    lib = load_library()
+    dev = require_device(ptr, idx, diag_pos, val, out)
+    if ptr.numel() != n + 1 or diag_pos.numel() != n or idx.numel() != val.numel() or not (ptr.dtype == idx.dtype == diag_pos.dtype):
+        raise RuntimeError(f"tsgu_csr_{kind}: {n} rows need a row pointer of {n + 1} words, {n} diagonal positions and as many values as "
+                           f"columns, all index arrays of one dtype; got {ptr.numel()}, {diag_pos.numel()}, {val.numel()} / {idx.numel()}")
+    ptr, idx, diag_pos, val = ptr.contiguous(), idx.contiguous(), diag_pos.contiguous(), val.contiguous()
+    if out is None:
+        out = torch.empty_like(val)
+    elif out.dtype != val.dtype or out.shape != val.shape or not out.is_contiguous():
+        raise RuntimeError(f"tsgu_csr_{kind}: `out` must be a contiguous array like the values")
+    info = torch.zeros((), dtype=torch.int64, device=dev)
+    if n == 0:
+        return out, info
+    work = torch.empty((lib.tsgu_csr_factor_work_bytes(n),), dtype=torch.uint8, device=dev)
+    launch(f"tsgu_csr_{kind}", dev, vtype_of(val), itype_of(ptr), n, idx.numel(), ptr, idx, diag_pos, val, float(shift), out, work, info,
+           int(wg_per_cu))
+    _defer_error_check(work[0:4].view(torch.int32), dev, f"tsgu_csr_{kind} (dependency wait)")
+    return out, info
 
 
 _PENDING = []            # (event or None, pinned / host int32 slot, what, tsgu status)

@@ -497,3 +497,49 @@ def bsr_attention_backward(walk, bh: int, bw: int, Q, K, V, dO, P, heads: int, s
     """(dQ, dK, dV, dA [nnzb, bh, bw] or None) by :func:`attention_backward`; dA folded back into the blocks (perm)."""
     dQ, dK, dV, dA = attention_backward(*walk, Q, K, V, dO, P, heads, scale, want_dA)
     return dQ, dK, dV, (dA.view(-1, bh, bw) if want_dA else None)
+
+
+def csr_factor(kind: str, crow: torch.Tensor, col: torch.Tensor, diag_pos: torch.Tensor, val: torch.Tensor, n: int, shift: float = 0.0):
+    """ILU(0) (``kind = "ilu0"``, the combined L \\ U array) or IC(0) (``"ic0"``, on the arrays of tril(A)) of a CSR matrix with
+    ascending, unique columns and a stored diagonal per row (include/tsgu_hip_factor.h has the recurrences): a plain row-by-row
+    loop in the value type.  Reference speed only — one Python iteration per stored lower entry; it exists so that CPU operands
+    have the semantics of the kernels (the ILU(0) bits included), not to be fast.  Returns (out, info) like `_backend.csr_factor`."""
+    import numpy as np
+
+    _cpu_only(crow, col, diag_pos, val)
+    ptr, idx, dpos = crow.numpy().astype(np.int64), col.numpy().astype(np.int64), diag_pos.numpy().astype(np.int64)
+    a = val.detach().numpy()
+    dt = a.dtype.type
+    out = np.empty_like(a)
+    scale = dt(1.0 + shift)
+    bad = 0
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            s, e, d = ptr[i], ptr[i + 1], dpos[i]
+            cols = idx[s:e]
+            w = a[s:e].copy()
+            w[d - s] = w[d - s] * scale
+            for q in range(d - s):
+                k = cols[q]
+                sk, ek, dk = ptr[k], ptr[k + 1], dpos[k]
+                if kind == "ilu0":
+                    w[q] = w[q] / out[dk]
+                    js, us = idx[dk + 1:ek], out[dk + 1:ek]
+                    m = np.searchsorted(cols, js)
+                    hit = (m < cols.size) & (cols[np.minimum(m, cols.size - 1)] == js)
+                    w[m[hit]] = w[m[hit]] - w[q] * us[hit]
+                else:
+                    js, ls = idx[sk:dk], out[sk:dk]
+                    m = np.searchsorted(cols[:q], js)
+                    hit = (m < q) & (cols[np.minimum(m, max(q - 1, 0))] == js)
+                    w[q] = (w[q] - np.sum(w[m[hit]] * ls[hit], dtype=a.dtype)) / out[dk]
+            if kind == "ilu0":
+                broke = w[d - s] == 0
+            else:
+                rad = w[d - s] - np.sum(w[:d - s] * w[:d - s], dtype=a.dtype)
+                broke = not rad > 0
+                w[d - s] = np.sqrt(rad)
+            if broke and not bad:
+                bad = i + 1
+            out[s:e] = w
+    return torch.from_numpy(out), torch.tensor(bad, dtype=torch.int64)

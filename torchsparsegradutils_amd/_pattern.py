@@ -1083,3 +1083,101 @@ def flat_block_diag(crow: torch.Tensor, col: torch.Tensor, n: int, m: int) -> Ro
     b = col.size(0)
     g = RowGather(crow, col, n, m, core=_core_for("csr", (crow, col), (b, n, m)))
     return flat_of(g)
+
+
+# ---- incomplete factorisations (sparse_factor.py) ----------------------------------------------------------------------------------
+class FactorPlan:
+    """What ILU(0) / IC(0) need of a square pattern, cached with it (``factor_plan``).
+
+    gather     the canonical CSR pattern as a RowGather without ``perm`` (columns ascending and unique per row): A's own plan,
+               index tensors included, when A's CSR is canonical already
+    perm       position of every canonical entry in A's value array (None: identity)
+    diag_pos   (n,) position of every row's diagonal in the canonical arrays (index dtype of the pattern)
+    ``lower()`` / ``upper()`` / ``strict_lower()``: the triangles of the pattern, derived on first use."""
+
+    __slots__ = ("gather", "perm", "diag_pos", "_parts")
+
+    def __init__(self, gather: RowGather, perm, diag_pos):
+        self.gather, self.perm, self.diag_pos = gather, perm, diag_pos
+        self._parts = {}
+
+    def canonical_values(self, values: torch.Tensor) -> torch.Tensor:
+        v = values.reshape(-1)
+        return v if self.perm is None else v.index_select(0, self.perm.to(torch.int64))
+
+    def _triangle(self, which: str):
+        got = self._parts.get(which)
+        if got is None:
+            g = self.gather
+            rows, col = g.row_indices(), g.col
+            mask = {"lower": col <= rows, "upper": col >= rows, "strict_lower": col < rows}[which]
+            pos = torch.nonzero(mask).reshape(-1)
+            counts = torch.bincount(rows[pos].to(torch.int64), minlength=g.n_rows)
+            crow = torch.zeros(g.n_rows + 1, dtype=g.crow.dtype, device=col.device)
+            crow[1:] = torch.cumsum(counts, 0)
+            got = self._parts[which] = (RowGather(crow, col[pos].contiguous(), g.n_rows, g.n_cols), pos)
+        return got
+
+    def lower(self):
+        """(RowGather of tril(A), positions of its entries in the canonical arrays, diagonal positions in the lower arrays)."""
+        lg, pos = self._triangle("lower")
+        dp = self._parts.get("lower_diag")
+        if dp is None:
+            dp = self._parts["lower_diag"] = (lg.crow[1:] - 1).contiguous()       # (ascending columns: the diagonal closes its row)
+        return lg, pos, dp
+
+    def upper(self):
+        return self._triangle("upper")
+
+    def strict_lower(self):
+        return self._triangle("strict_lower")
+
+
+def factor_plan(g: RowGather) -> FactorPlan:
+    """The FactorPlan of a 2-D square pattern.  Checked once per pattern with one host read (a second one when the columns have to
+    be sorted first): columns unique per row and a stored diagonal in every row, else ValueError naming the first offending row.
+    Columns that are merely unsorted (and the stable row order of un-coalesced COO entries) are canonicalised through a cached
+    permutation."""
+    fp = g.core.own.get("factor")
+    if fp is not None:
+        if isinstance(fp, ValueError):
+            raise fp
+        return fp
+    if g.batch is not None or g.n_rows != g.n_cols:
+        raise ValueError("factor_plan: a 2-D square pattern is required")
+    n, dev = g.n_rows, g.col.device
+    rows, col, perm = g.row_indices(), g.col, g.perm
+
+    def survey(rows, col):
+        # [entries that do not ascend strictly within their row, first row that stores a column twice, first row without a diagonal]
+        key = rows.to(torch.int64) * n + col.to(torch.int64)
+        step = key[1:] - key[:-1]
+        has = torch.zeros(n + 1, dtype=torch.bool, device=dev)
+        has[torch.where(rows == col, rows.to(torch.int64), n)] = True
+        ar = torch.arange(n + 1, dtype=torch.int64, device=dev)
+        missing = torch.where(has[:n], n, ar[:n]).min() if n else ar[:1].sum() * 0 + n
+        if step.numel():
+            dup = torch.where(step == 0, rows[1:].to(torch.int64), n).min()
+            bad = (step <= 0).sum()
+        else:
+            dup, bad = missing * 0 + n, missing * 0
+        return [int(v) for v in torch.stack((bad, dup, missing)).tolist()]
+
+    bad, dup, missing = survey(rows, col)
+    if bad and dup >= n:            # unsorted (or a duplicate the stored order hides): sort, then look again
+        order = torch.argsort(rows.to(torch.int64) * n + col.to(torch.int64), stable=True)
+        col = col[order].contiguous()
+        perm = order if perm is None else perm.to(torch.int64)[order]
+        bad, dup, missing = survey(rows, col)
+    err = None
+    if dup < n or bad:
+        err = ValueError(f"sparse factorisation: row {dup if dup < n else 0} stores a column more than once")
+    elif missing < n:
+        err = ValueError(f"sparse factorisation: row {missing} does not store its diagonal")
+    if err is not None:
+        g.core.own["factor"] = err
+        raise err
+    canonical = g if (perm is None and col is g.col) else RowGather(g.crow, col, n, n)
+    diag_pos = torch.nonzero(canonical.row_indices() == col).reshape(-1).to(g.crow.dtype).contiguous()
+    fp = g.core.own["factor"] = FactorPlan(canonical, None if perm is None else perm.contiguous(), diag_pos)
+    return fp

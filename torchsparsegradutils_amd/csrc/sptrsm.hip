@@ -66,9 +66,7 @@ __global__ __launch_bounds__(kBlock) void sptrsm_syncfree_kernel(const TrsmParam
     const int ncls = P.wgc * kTrsmWaves;
     unsigned long long* const counter = &work->class_ticket[(slot * 64 + (P.wgc > 1 ? wg : tile)) * 16];
     for (;;) {
-        unsigned long long t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = __shfl(t, 0, kWave) * ncls + cls;
+        const unsigned long long t = next_row_ticket(counter, lane, ncls, cls);
         if (t >= (unsigned long long)P.n) break;
         const int64_t row = P.lower ? (int64_t)t : P.n - 1 - (int64_t)t;
         const int64_t s = (int64_t)ptr[row];
@@ -162,12 +160,7 @@ int sptrsm_launch(const TrsmParams& P, int n_cu, int wg_per_cu, hipStream_t stre
     // row, a few dozen levels of thousands of rows) is bound by the rows in flight instead — a wave spends ~3 us of dependent
     // loads per row — and wants every wave the CU can hold.  The caller chooses (a measured choice per pattern in
     // sparse_solve.py); the result does not depend on it.  Never more waves than rows.
-    if (wg_per_cu < 1) wg_per_cu = 1;
-    if (wg_per_cu > 8) wg_per_cu = 8;
-    int64_t blocks = (int64_t)n_cu * wg_per_cu;
-
-    const int64_t need = (P.n + 3) / 4;
-    if (blocks > need) blocks = need;
+    int64_t blocks = persistent_blocks(n_cu, wg_per_cu, P.n);
     if (tiles > 1) {
         blocks = blocks / tiles;
         if (blocks < 1) blocks = 1;
@@ -217,7 +210,7 @@ int tsgu_csr_sptrsm(int vtype, int itype, int64_t n, int64_t nnz,
     P.work = static_cast<TrsmWork*>(work);
     P.lower = lower;
     P.unit = unit;
-    P.timeout_ticks = 400000000LL;  // 4 s at the 100 MHz wall clock
+    P.timeout_ticks = kSpinTimeoutTicks;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return with_types<float, double, bf16_t>(vtype, itype, [&](auto v, auto i) {
         return sptrsm_launch<decltype(v), decltype(i)>(P, n_cu, workgroups_per_cu, s);

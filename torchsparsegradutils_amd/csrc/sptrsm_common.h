@@ -1,6 +1,8 @@
 // What the two kernel families of the triangular solve share (csrc/sptrsm.hip: the sync-free CSR sweep; csrc/sptrsm_lattice.hip:
 // the line sweep on stencil factors): the work buffer with its tickets and error word, the "not ready" tag of every value type,
-// the kernel that pre-fills X with it, and the sum over a column's entry lanes.
+// the kernel that pre-fills X with it, and the sum over a column's entry lanes.  The ordered row tickets, the time bound of every spin
+// and the size of the persistent grid are shared with the incomplete factorisations as well (csrc/ilu_impl.h), whose rows depend
+// on one another exactly as the rows of a lower solve do.
 #pragma once
 
 #include "tsgu_common.h"
@@ -21,8 +23,30 @@ struct TrsmWork {
     // whatever the number of waves).  Forward progress, per class: a counter hands its rows out in order, so every row of the class
     // below the lowest unfinished one is finished and the waves that held them are free to take it; every class has a resident wave
     // (the grid is persistent and never smaller than `wgc` workgroups).
-    unsigned long long class_ticket[kTrsmWaves * 64 * 16];
+    unsigned long long class_ticket[kTrsmWaves * 64 * 16];   // (= kTicketWords, below)
 };
+
+// ---- ordered row tickets, bounded spins, persistent grid (sptrsm.hip, ilu_impl.h) ----------------------------------------------
+constexpr int kTicketStride = 16;                         // counters 128 bytes apart
+constexpr int kTicketWords = kTrsmWaves * 64 * kTicketStride;
+constexpr long long kSpinTimeoutTicks = 400000000LL;      // 4 s at the 100 MHz wall clock
+
+// The next row of class `cls` out of `ncls` (rows ≡ cls mod ncls, in order), drawn by lane 0 for its wave.  The caller stops at
+// the first ticket >= n.
+__device__ __forceinline__ unsigned long long next_row_ticket(unsigned long long* counter, int lane, int ncls, int cls) {
+    unsigned long long t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return __shfl(t, 0, kWave) * ncls + cls;
+}
+
+// Workgroups of the persistent grid: `wg_per_cu` (1 … 8) per compute unit, never more waves than rows.
+inline int64_t persistent_blocks(int n_cu, int wg_per_cu, int64_t n_rows) {
+    if (wg_per_cu < 1) wg_per_cu = 1;
+    if (wg_per_cu > 8) wg_per_cu = 8;
+    int64_t blocks = (int64_t)n_cu * wg_per_cu;
+    const int64_t need = (n_rows + kTrsmWaves - 1) / kTrsmWaves;
+    return blocks > need ? need : blocks;
+}
 
 template <typename V>
 struct Sentinel;

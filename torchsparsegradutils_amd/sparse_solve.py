@@ -97,14 +97,16 @@ class _TriOperand:
         return torch.sparse_coo_tensor(self.coo_indices, grad_values, self.shape)
 
 
-def _solve(plan: _pt.RowGather, values, rhs, upper: bool, unit: bool, transpose: bool):
-    """X = op(A)^{-1} rhs on the 2-D plan (reference _compat.py:42-48 semantics)."""
+def _solve(plan: _pt.RowGather, values, rhs, upper: bool, unit: bool, transpose: bool, combined: bool = False):
+    """X = op(A)^{-1} rhs on the 2-D plan (reference _compat.py:42-48 semantics).  `combined`: the value array holds BOTH triangles
+    (the L \\ U array of sparse_ilu0): the sync-free sweep ignores the entries on the other side of the diagonal; the line sweep,
+    whose tables are derived from the whole pattern, is not asked."""
     if not rhs.is_cuda:     # CPU operands: the legacy ATen call itself, as the reference makes it (_cpu.py)
         from . import _cpu
 
         return _cpu.sptrsm(plan, values, rhs, upper, unit, transpose)
     lower = upper if transpose else not upper        # (transposed: rows of Aᵀ; the selected triangle flips side)
-    tables = _lattice_tables(plan, values, rhs, lower, transpose)
+    tables = None if combined else _lattice_tables(plan, values, rhs, lower, transpose)
     if tables is not None:
         # a stencil factor on a lattice: the line sweep (csrc/sptrsm_lattice.hip) — the same bits, no wall-clock trial, and the
         # transposed solve walks A's own arrays (no transposed pattern is built for it)
