@@ -235,6 +235,12 @@ SIGNATURES_FACTOR = {
     "tsgu_csr_ic0": (_int, list(_FACTOR_ARGS)),
 }
 
+# the additive entries of include/tsgu_hip_fsai.h (same library, same ABI version)
+SIGNATURES_FSAI = {
+    "tsgu_csr_fsai_geometry": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_fsai": (_int, [_int, _int, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -259,7 +265,7 @@ def load_library():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
                                   *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items(), *SIGNATURES_BSR.items(),
-                                  *SIGNATURES_BSR_ATTENTION.items(), *SIGNATURES_FACTOR.items()):
+                                  *SIGNATURES_BSR_ATTENTION.items(), *SIGNATURES_FACTOR.items(), *SIGNATURES_FSAI.items()):
             fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
             fn.restype = res
             fn.argtypes = args
@@ -1394,6 +1400,40 @@ def csr_factor(kind: str, ptr, idx, diag_pos, val, n: int, shift: float = 0.0, w
     launch(f"tsgu_csr_{kind}", dev, vtype_of(val), itype_of(ptr), n, idx.numel(), ptr, idx, diag_pos, val, float(shift), out, work, info,
            int(wg_per_cu))
     _defer_error_check(work[0:4].view(torch.int32), dev, f"tsgu_csr_{kind} (dependency wait)")
+    return out, info
+
+
+def fsai_geometry(dtype: torch.dtype):
+    """(row_capacity, rows_per_block) of the FSAI build for `dtype`: the longest row of the pattern S (the largest local system)
+    the kernel accepts, and the rows a workgroup takes at a time."""
+    cap, rows = _int(0), _int(0)
+    check(load_library().tsgu_csr_fsai_geometry(_VTYPE[dtype], ctypes.byref(cap), ctypes.byref(rows)), "tsgu_csr_fsai_geometry")
+    return cap.value, rows.value
+
+
+def csr_fsai(a_ptr, a_idx, a_val, s_ptr, s_idx, n: int, order=None, wg_per_cu: int = 8):
+    """The values of the FSAI factor G on the lower pattern (s_ptr, s_idx) for the CSR (a_ptr, a_idx, a_val) of tril(A)
+    (include/tsgu_hip_fsai.h).  Both patterns: columns ascending and unique per row, the diagonal last — the caller's plan has
+    checked that, and that no row of S exceeds `fsai_geometry`'s capacity.  `order`: the rows in the order the waves take them
+    (speed only).  Returns (out, info): `info` a device int64, 0 or 1 + the lowest row whose local matrix was not positive
+    definite.  Nothing in the kernel waits, so there is no work buffer and nothing is read back here."""
+    if a_val.dtype not in FACTOR_DTYPES:
+        raise TypeError(f"tsgu_csr_fsai: float32 and float64 values only, got {a_val.dtype}")
+    dev = require_device(a_ptr, a_idx, a_val, s_ptr, s_idx, order)
+    index = [t for t in (a_ptr, a_idx, s_ptr, s_idx, order) if t is not None]
+    if (a_ptr.numel() != n + 1 or s_ptr.numel() != n + 1 or a_idx.numel() != a_val.numel() or (order is not None and order.numel() != n)
+            or any(t.dtype != a_ptr.dtype for t in index)):
+        raise RuntimeError(f"tsgu_csr_fsai: {n} rows need two row pointers of {n + 1} words, as many values as columns of A, an "
+                           f"`order` of {n} rows, and all index arrays of one dtype; got {a_ptr.numel()}, {s_ptr.numel()}, "
+                           f"{a_val.numel()} / {a_idx.numel()}" + ("" if order is None else f", {order.numel()}"))
+    a_ptr, a_idx, a_val, s_ptr, s_idx = (t.contiguous() for t in (a_ptr, a_idx, a_val, s_ptr, s_idx))
+    order = None if order is None else order.contiguous()
+    out = torch.empty(s_idx.numel(), dtype=a_val.dtype, device=dev)
+    info = torch.zeros((), dtype=torch.int64, device=dev)
+    if n == 0:
+        return out, info
+    launch("tsgu_csr_fsai", dev, vtype_of(a_val), itype_of(a_ptr), n, a_ptr, a_idx, a_val, s_ptr, s_idx, s_idx.numel(), order, out, info,
+           int(wg_per_cu))
     return out, info
 
 

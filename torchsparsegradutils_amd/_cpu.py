@@ -543,3 +543,41 @@ def csr_factor(kind: str, crow: torch.Tensor, col: torch.Tensor, diag_pos: torch
                 bad = i + 1
             out[s:e] = w
     return torch.from_numpy(out), torch.tensor(bad, dtype=torch.int64)
+
+
+def csr_fsai(a_crow: torch.Tensor, a_col: torch.Tensor, a_val: torch.Tensor, s_crow: torch.Tensor, s_col: torch.Tensor, n: int):
+    """The FSAI factor G on the lower pattern (s_crow, s_col) for the CSR of tril(A) (include/tsgu_hip_fsai.h has the semantics;
+    both patterns with ascending, unique columns and the diagonal last): a plain loop over the rows, one dense Cholesky
+    factorisation and one triangular solve each, in the value type.  Reference speed only.  A row whose local matrix is not
+    positive definite is filled with NaN.  Returns (out, info) like `_backend.csr_fsai`."""
+    import numpy as np
+
+    _cpu_only(a_crow, a_col, a_val, s_crow, s_col)
+    aptr, aidx = a_crow.numpy().astype(np.int64), a_col.numpy().astype(np.int64)
+    sptr, sidx = s_crow.numpy().astype(np.int64), s_col.numpy().astype(np.int64)
+    a = a_val.detach().numpy()
+    out = np.empty(sidx.size, dtype=a.dtype)
+    bad = 0
+    for i in range(n):
+        J = sidx[sptr[i]:sptr[i + 1]]
+        m = J.size
+        M = np.zeros((m, m), dtype=a.dtype)
+        for t in range(m):                           # row j_t of tril(A) against J[0 … t]
+            s, e = aptr[J[t]], aptr[J[t] + 1]
+            cols = aidx[s:e]
+            b = np.searchsorted(J[:t + 1], cols)
+            hit = (b <= t) & (J[np.minimum(b, t)] == cols)
+            M[t, b[hit]] = a[s:e][hit]
+        M = M + np.tril(M, -1).T
+        rhs = np.zeros(m, dtype=a.dtype)
+        rhs[m - 1:] = 1
+        try:
+            if not np.all(np.isfinite(M)):
+                raise np.linalg.LinAlgError
+            L = np.linalg.cholesky(M)
+            g = np.linalg.solve(L.T, rhs)            # = y / sqrt(y_m) of A[J,J]·y = e_m
+        except np.linalg.LinAlgError:
+            g = np.full(m, np.nan, dtype=a.dtype)
+            bad = bad or i + 1
+        out[sptr[i]:sptr[i + 1]] = g
+    return torch.from_numpy(out), torch.tensor(bad, dtype=torch.int64)

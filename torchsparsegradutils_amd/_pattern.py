@@ -1181,3 +1181,56 @@ def factor_plan(g: RowGather) -> FactorPlan:
     diag_pos = torch.nonzero(canonical.row_indices() == col).reshape(-1).to(g.crow.dtype).contiguous()
     fp = g.core.own["factor"] = FactorPlan(canonical, None if perm is None else perm.contiguous(), diag_pos)
     return fp
+
+
+# ---- factorised sparse approximate inverse (sparse_fsai.py) ---------------------------------------------------------------------------
+FSAI_CLASSES = (8, 16, 32)      # a row of S of at most 8 / 16 / 32 / more entries is built by 8 / 16 / 32 / 64 lanes (csrc/fsai_impl.h)
+
+
+class FsaiPlan:
+    """What an FSAI build needs of the pattern S it is built on, cached with the tensor that carries S (``fsai_plan``).
+
+    factor     the FactorPlan of that tensor's pattern: S is its ``lower()``
+    longest    (row, entries) of the longest row of S
+    ``view(index dtype)``: (RowGather of S, row order) in the index dtype of A — S's own arrays when the dtypes agree.  The order
+    lists the rows by size class (stable: ascending within a class), so that a wave holds rows of one class; None when S has one
+    class only.  Gᵀ's pattern, with the ``perm`` that makes its value array one ``index_select`` of G's, is the ``.transposed``
+    of that RowGather."""
+
+    __slots__ = ("factor", "longest", "_order", "_views")
+
+    def __init__(self, factor: FactorPlan, longest, order):
+        self.factor, self.longest, self._order = factor, longest, order
+        self._views = {}
+
+    def view(self, idt: torch.dtype):
+        got = self._views.get(idt)
+        if got is None:
+            lg = self.factor.lower()[0]
+            if lg.crow.dtype != idt:
+                lg = RowGather(lg.crow.to(idt), lg.col.to(idt), lg.n_rows, lg.n_cols)
+            got = self._views[idt] = (lg, None if self._order is None else self._order.to(idt).contiguous())
+        return got
+
+
+def fsai_plan(g: RowGather, capacity: int) -> FsaiPlan:
+    """The FsaiPlan of the 2-D square pattern whose lower triangle is S.  On top of ``factor_plan``'s check (unique columns, every
+    diagonal stored) one host read per pattern: the longest row of S and the span of the size classes.  A row longer than
+    `capacity` (``_backend.fsai_geometry``) is a ValueError naming it."""
+    plan = g.core.own.get("fsai")
+    if plan is None:
+        fp = factor_plan(g)
+        lg = fp.lower()[0]
+        if lg.n_rows:
+            lens = (lg.crow[1:] - lg.crow[:-1]).to(torch.int64)
+            cls = sum((lens > c).to(torch.int64) for c in FSAI_CLASSES)
+            row, m, lo, hi = (int(v) for v in torch.stack((lens.argmax(), lens.max(), cls.min(), cls.max())).tolist())
+            order = torch.argsort(cls, stable=True) if lo != hi else None
+        else:
+            row, m, order = 0, 0, None
+        plan = g.core.own["fsai"] = FsaiPlan(fp, (row, m), order)
+    row, m = plan.longest
+    if m > capacity:
+        raise ValueError(f"sparse_fsai: row {row} of the pattern stores {m} lower-triangular entries, more than the {capacity} a local "
+                         "system may have (a row costs m³: choose a sparser pattern)")
+    return plan
