@@ -1,4 +1,6 @@
-"""Argument vectors for the C ABI refusal tests (test_abi_refusals_cpu.py, test_gpu_abi_refusals.py).
+"""The shared C ABI test helper: the one parser of the headers under include/ with the parameter classes
+(test_abi_conformance_cpu.py), the status codes, and the argument vectors of the refusal tests (test_abi_refusals_cpu.py,
+test_gpu_abi_refusals.py).
 
 Every launcher of include/tsgu_hip.h (an entry point whose last two parameters are `device, stream`) gets one BASE call that
 passes all of its argument checks: 8 rows, 8 stored entries, the family's smallest width, plan structures that pass the
@@ -11,7 +13,7 @@ import re
 
 from torchsparsegradutils_amd import _backend
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tsgu_hip.h")
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 
 OK, BAD_DTYPE, BAD_ARG, TOO_LARGE, LAUNCH, RUNTIME = 0, -1, -2, -3, -4, -5
 
@@ -95,23 +97,43 @@ _BY_NAME = dict(batch=1, b_col_stride=1, c_col_stride=1, y_col_stride=1, e_col_s
                 b_batch_stride=64, c_batch_stride=64, g_batch_stride=64, gb_batch_stride=64)
 
 
-def _parse_header():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"^(?:int|int64_t)\s+(tsgu_\w+)\(([^)]*)\);", text, flags=re.M):
-        params = []
-        for raw in m.group(2).split(","):
+def prototypes(header):
+    """The entries include/`header` declares, in declaration order: [(name, [(parameter name, type text), ...]), ...].  Comments
+    are stripped first; a parameter list may span lines; `(void)` is an empty list."""
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
+    out = []
+    for entry, params in re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        pairs = []
+        for raw in params.split(","):
             raw = " ".join(raw.split())
-            if raw == "void":
-                continue
-            name = re.search(r"(\w+)$", raw).group(1)
-            params.append((name, raw[: -len(name)].strip()))
-        out[m.group(1)] = params
+            if raw != "void":
+                name = re.search(r"(\w+)$", raw).group(1)
+                pairs.append((name, raw[: -len(name)].strip()))
+        out.append((entry, pairs))
     return out
 
 
-PARAMS = _parse_header()
+def klass_of_decl(type_text):
+    """Class of a parameter of a prototype: pointer / 64-bit integer / double / int."""
+    if "*" in type_text:
+        return "ptr"
+    if re.search(r"\bint64_t\b", type_text):
+        return "i64"
+    if re.search(r"\bdouble\b", type_text):
+        return "dbl"
+    if re.search(r"\b(int|tsgu_vtype|tsgu_itype)\b", type_text):
+        return "int"
+    raise AssertionError(f"unclassified parameter type {type_text!r}")
+
+
+def klass_of_ctype(t):
+    """Class of an entry of a ctypes `argtypes` list, in the words of `klass_of_decl`."""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
+        return "ptr"
+    return {ctypes.c_int64: "i64", ctypes.c_int: "int", ctypes.c_double: "dbl"}[t]
+
+
+PARAMS = dict(prototypes("tsgu_hip.h"))
 LAUNCHERS = sorted(n for n, ps in PARAMS.items() if len(ps) >= 2 and [q[0] for q in ps[-2:]] == ["device", "stream"])
 
 

@@ -1,5 +1,5 @@
 """CPU-side checks: index helpers bit-exact vs the reference's golden outputs, validation messages,
-the C-ABI library exports every symbol the header declares, and the product refuses CPU tensors."""
+the host-side helpers of the C-ABI library, and the product refuses CPU tensors."""
 
 import ctypes
 import os
@@ -145,19 +145,11 @@ def test_cpu_solvers_run_on_tensor_ops():
         assert not x.is_cuda and torch.allclose(x, torch.full((3, 2), 0.5))
 
 
-def test_abi_library_exports_every_declared_symbol():
+def test_host_side_helpers_of_the_abi():
+    """The entries that answer on the host (exports and signatures: tests/test_abi_conformance_cpu.py)."""
     from torchsparsegradutils_amd import _backend
 
-    header = open(os.path.join(ROOT, "include", "tsgu_hip.h")).read()
-    declared = set(re.findall(r"\b(tsgu_[a-z0-9_]+)\s*\(", header))
-    assert len(declared) >= 15
     lib = _backend.load_library()  # loads without a GPU; no compute call is made here
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), f"{name} declared in include/tsgu_hip.h but not exported"
-        assert name in _backend.SIGNATURES, f"{name} has no ctypes signature"
-    assert set(_backend.SIGNATURES) <= declared
-    assert lib.tsgu_abi_version() == 7
     # row-pair geometry: (rows per workgroup, entry lanes) per (value type, p); unsupported shapes are refused
     r, e = ctypes.c_int(0), ctypes.c_int(0)
     for vt, p_, want in ((_backend.TSGU_F32, 32, (64, 1)), (_backend.TSGU_F32, 64, (32, 1)), (_backend.TSGU_F32, 16, (64, 2)),
@@ -201,47 +193,6 @@ def test_product_never_imports_the_oracle():
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, re.M), f
                 assert "liboracle" not in src, f
-
-
-def test_ctypes_signatures_agree_with_the_header_prototypes():
-    """Every prototype of include/tsgu_hip.h against `_backend.SIGNATURES`: the same number of parameters, and for each one the
-    same class (pointer / 64-bit integer / int / double) — a mismatch would only show as stack garbage on the GPU box."""
-    import ctypes as C
-
-    from torchsparsegradutils_amd import _backend
-
-    header = open(os.path.join(ROOT, "include", "tsgu_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    protos = re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header, flags=re.S)
-    assert len(protos) >= 40
-
-    def klass_of_decl(decl):
-        decl = " ".join(decl.split())
-        if decl == "void":
-            return None
-        if "*" in decl:
-            return "ptr"
-        if re.search(r"\bint64_t\b", decl):
-            return "i64"
-        if re.search(r"\bdouble\b", decl):
-            return "dbl"
-        if re.search(r"\b(int|tsgu_vtype|tsgu_itype)\b", decl):
-            return "int"
-        raise AssertionError(f"unclassified parameter {decl!r}")
-
-    def klass_of_ctype(t):
-        if t in (C.c_void_p, C.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
-            return "ptr"
-        return {C.c_int64: "i64", C.c_int: "int", C.c_double: "dbl"}[t]
-
-    seen = set()
-    for name, params in protos:
-        want = [k for k in (klass_of_decl(d) for d in params.split(",")) if k is not None]
-        _, argtypes = _backend.SIGNATURES[name]
-        got = [klass_of_ctype(t) for t in argtypes]
-        assert got == want, (name, got, want)
-        seen.add(name)
-    assert seen == set(_backend.SIGNATURES)
 
 
 def test_cpu_tensors_take_the_torch_op_path_and_mixed_devices_raise():

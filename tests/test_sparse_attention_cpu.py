@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from _abi_cases import BAD_ARG, BAD_DTYPE, OK, TOO_LARGE
 import _attention_ref as ar
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, _pattern
@@ -284,75 +285,6 @@ def test_nothing_is_densified(monkeypatch):
 # C ABI: the third header
 
 
-HEADER = os.path.join(ROOT, "include", "tsgu_hip_attention.h")
-ENTRIES = ("tsgu_csr_attention_supported", "tsgu_csr_attention_geometry", "tsgu_csr_attention", "tsgu_csr_attention_backward_rows",
-           "tsgu_csr_attention_backward_cols")
-LAUNCHERS = ENTRIES[2:]
-
-
-def _prototypes(path):
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-
-
-def test_the_symbols_are_exported_and_bound():
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    for name in ENTRIES:
-        assert hasattr(raw, name), f"{name} is not exported by libtsgu_hip.so"
-    assert tuple(_backend.SIGNATURES_ATTENTION) == ENTRIES
-    assert [n for n, _ in _prototypes(HEADER)] == list(ENTRIES)
-    lib = _backend.load_library()
-    for name in ENTRIES:
-        assert getattr(lib, name).argtypes == _backend.SIGNATURES_ATTENTION[name][1]
-
-
-def test_ctypes_signatures_agree_with_the_attention_header_prototypes():
-    """tests/test_sparse_softmax_cpu.py::test_ctypes_signatures_agree_with_the_softmax_header_prototypes, for the third header."""
-    C = ctypes
-
-    def klass_of_decl(decl):
-        decl = " ".join(decl.split())
-        if decl == "void":
-            return None
-        if "*" in decl:
-            return "ptr"
-        if re.search(r"\bint64_t\b", decl):
-            return "i64"
-        if re.search(r"\bdouble\b", decl):
-            return "dbl"
-        if re.search(r"\b(int|tsgu_vtype|tsgu_itype)\b", decl):
-            return "int"
-        raise AssertionError(f"unclassified parameter {decl!r}")
-
-    def klass_of_ctype(t):
-        if t in (C.c_void_p, C.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
-            return "ptr"
-        return {C.c_int64: "i64", C.c_int: "int", C.c_double: "dbl"}[t]
-
-    seen = set()
-    for name, params in _prototypes(HEADER):
-        want = [k for k in (klass_of_decl(d) for d in params.split(",")) if k is not None]
-        got = [klass_of_ctype(t) for t in _backend.SIGNATURES_ATTENTION[name][1]]
-        assert got == want, (name, got, want)
-        seen.add(name)
-    assert seen == set(_backend.SIGNATURES_ATTENTION)
-    for name, params in _prototypes(HEADER):
-        if name in LAUNCHERS:
-            assert [" ".join(p.split()) for p in params.split(",")][-2:] == ["int device", "void* stream"], name
-
-
-def test_the_older_headers_and_the_abi_version_are_untouched():
-    first = {n for n, _ in _prototypes(os.path.join(ROOT, "include", "tsgu_hip.h"))}
-    second = {n for n, _ in _prototypes(os.path.join(ROOT, "include", "tsgu_hip_softmax.h"))}
-    assert first == set(_backend.SIGNATURES) and second == set(_backend.SIGNATURES_SOFTMAX)
-    assert not any("attention" in n for n in first | second)
-    assert not set(ENTRIES) & (set(_backend.SIGNATURES) | set(_backend.SIGNATURES_SOFTMAX))
-    assert _backend.load_library().tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    assert "TSGU_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "tsgu_hip.h")).read()
-    assert '#include "tsgu_hip.h"' in open(HEADER).read()
-
-
-OK, BAD_DTYPE, BAD_ARG, TOO_LARGE = 0, -1, -2, -3
 FAKE = 0x7F0000001000          # a 16-byte aligned address that is never dereferenced: every call below is refused on the host
 
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from _abi_cases import BAD_ARG, BAD_DTYPE, OK
 import _factor_ref as fr
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, _pattern, sparse_ic0, sparse_ilu0
@@ -242,71 +243,6 @@ def test_ic0_factor_as_precision_tril_on_cpu():
 # C ABI: the header of the factorisations
 
 HEADER = os.path.join(ROOT, "include", "tsgu_hip_factor.h")
-ENTRIES = ("tsgu_csr_factor_work_bytes", "tsgu_csr_factor_geometry", "tsgu_csr_ilu0", "tsgu_csr_ic0")
-LAUNCHERS = ENTRIES[2:]
-
-
-def _prototypes(path):
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-
-
-def test_the_symbols_are_exported_and_bound():
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    for name in ENTRIES:
-        assert hasattr(raw, name), f"{name} is not exported by libtsgu_hip.so"
-    assert tuple(_backend.SIGNATURES_FACTOR) == ENTRIES
-    assert [n for n, _ in _prototypes(HEADER)] == list(ENTRIES)
-    lib = _backend.load_library()
-    for name in ENTRIES:
-        assert getattr(lib, name).argtypes == _backend.SIGNATURES_FACTOR[name][1]
-        assert getattr(lib, name).restype == _backend.SIGNATURES_FACTOR[name][0]
-
-
-def test_ctypes_signatures_agree_with_the_header_prototypes():
-    C = ctypes
-
-    def klass_of_decl(decl):
-        decl = " ".join(decl.split())
-        if decl == "void":
-            return None
-        if "*" in decl:
-            return "ptr"
-        if re.search(r"\bint64_t\b", decl):
-            return "i64"
-        if re.search(r"\bdouble\b", decl):
-            return "dbl"
-        if re.search(r"\b(int|tsgu_vtype|tsgu_itype)\b", decl):
-            return "int"
-        raise AssertionError(f"unclassified parameter {decl!r}")
-
-    def klass_of_ctype(t):
-        if t in (C.c_void_p, C.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
-            return "ptr"
-        return {C.c_int64: "i64", C.c_int: "int", C.c_double: "dbl"}[t]
-
-    seen = set()
-    for name, params in _prototypes(HEADER):
-        want = [k for k in (klass_of_decl(d) for d in params.split(",")) if k is not None]
-        got = [klass_of_ctype(t) for t in _backend.SIGNATURES_FACTOR[name][1]]
-        assert got == want, (name, got, want)
-        seen.add(name)
-        if name in LAUNCHERS:
-            assert [" ".join(p.split()) for p in params.split(",")][-2:] == ["int device", "void* stream"], name
-    assert seen == set(_backend.SIGNATURES_FACTOR)
-
-
-def test_the_older_headers_and_the_abi_version_are_untouched():
-    for header, table in (("tsgu_hip.h", _backend.SIGNATURES), ("tsgu_hip_mm_reduce.h", _backend.SIGNATURES_MM_REDUCE)):
-        names = {n for n, _ in _prototypes(os.path.join(ROOT, "include", header))}
-        assert names == set(table), header
-        assert not set(ENTRIES) & set(table)
-    assert _backend.load_library().tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    assert '#include "tsgu_hip.h"' in open(HEADER).read()
-    assert "tsgu_hip_factor.h" in open(os.path.join(ROOT, "torchsparsegradutils_amd", "csrc", "Makefile")).read()
-
-
-OK, BAD_DTYPE, BAD_ARG = 0, -1, -2
 FAKE = 0x7F0000001000          # an address that is never dereferenced: every call below is refused on the host
 
 
@@ -317,7 +253,7 @@ def _call(lib, name, **kw):
     return getattr(lib, name)(*a.values())
 
 
-@pytest.mark.parametrize("name", LAUNCHERS)
+@pytest.mark.parametrize("name", ["tsgu_csr_ilu0", "tsgu_csr_ic0"])
 def test_launcher_refusals_on_the_host(name):
     lib = _backend.load_library()
     # the base call passes every check but the device's: device = -1 is refused by set_device, before any HIP call

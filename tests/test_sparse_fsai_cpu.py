@@ -3,12 +3,12 @@ oracle, M(R), every refusal, and the C-ABI header of the build with its host-sid
 
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+from _abi_cases import BAD_ARG, BAD_DTYPE, OK
 import _fsai_ref as sr
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_fsai
@@ -266,56 +266,6 @@ def test_breakdown_is_reported_with_its_row():
 # ---------------------------------------------------------------------------------------------------------------------------
 # the header
 
-HEADER = os.path.join(ROOT, "include", "tsgu_hip_fsai.h")
-ENTRIES = ("tsgu_csr_fsai_geometry", "tsgu_csr_fsai")
-
-
-def _prototypes(path):
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-
-
-def test_the_symbols_are_exported_and_bound():
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    for name in ENTRIES:
-        assert hasattr(raw, name), f"{name} is not exported by libtsgu_hip.so"
-    assert tuple(_backend.SIGNATURES_FSAI) == ENTRIES
-    assert [n for n, _ in _prototypes(HEADER)] == list(ENTRIES)
-    lib = _backend.load_library()
-    for name in ENTRIES:
-        assert getattr(lib, name).argtypes == _backend.SIGNATURES_FSAI[name][1]
-        assert getattr(lib, name).restype == _backend.SIGNATURES_FSAI[name][0]
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    assert '#include "tsgu_hip.h"' in open(HEADER).read()
-    assert "tsgu_hip_fsai.h" in open(os.path.join(ROOT, "torchsparsegradutils_amd", "csrc", "Makefile")).read()
-
-
-def test_ctypes_signatures_agree_with_the_header_prototypes():
-    C = ctypes
-
-    def klass_of_decl(decl):
-        decl = " ".join(decl.split())
-        if "*" in decl:
-            return "ptr"
-        if re.search(r"\bint64_t\b", decl):
-            return "i64"
-        if re.search(r"\bint\b", decl):
-            return "int"
-        raise AssertionError(f"unclassified parameter {decl!r}")
-
-    def klass_of_ctype(t):
-        if t in (C.c_void_p, C.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
-            return "ptr"
-        return {C.c_int64: "i64", C.c_int: "int"}[t]
-
-    protos = dict(_prototypes(HEADER))
-    assert set(protos) == set(_backend.SIGNATURES_FSAI)
-    for name, params in protos.items():
-        assert [klass_of_ctype(t) for t in _backend.SIGNATURES_FSAI[name][1]] == [klass_of_decl(d) for d in params.split(",")], name
-    assert [" ".join(p.split()) for p in protos["tsgu_csr_fsai"].split(",")][-2:] == ["int device", "void* stream"]
-
-
-OK, BAD_DTYPE, BAD_ARG = 0, -1, -2
 FAKE = 0x7F0000001000          # an address that is never dereferenced: every call below is refused on the host
 
 

@@ -18,6 +18,7 @@ import re
 import pytest
 import torch
 
+from _abi_cases import BAD_ARG, BAD_DTYPE, OK, TOO_LARGE
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, _pattern
 from torchsparsegradutils_amd import sparse_log_softmax, sparse_softmax          # (ImportError before the operators existed)
@@ -358,69 +359,6 @@ def test_output_and_gradient_carry_the_inputs_index_tensors(layout, index_dtype,
 # C ABI: the second header
 
 
-HEADER = os.path.join(ROOT, "include", "tsgu_hip_softmax.h")
-ENTRIES = ("tsgu_segment_softmax_workspace", "tsgu_segment_softmax", "tsgu_segment_softmax_backward")
-
-
-def _prototypes(path):
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-
-
-def test_the_symbols_are_exported_and_bound():
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    for name in ENTRIES:
-        assert hasattr(raw, name), f"{name} is not exported by libtsgu_hip.so"
-    assert tuple(_backend.SIGNATURES_SOFTMAX) == ENTRIES
-    assert [n for n, _ in _prototypes(HEADER)] == list(ENTRIES)
-    lib = _backend.load_library()
-    for name in ENTRIES:
-        assert getattr(lib, name).argtypes == _backend.SIGNATURES_SOFTMAX[name][1]
-
-
-def test_ctypes_signatures_agree_with_the_softmax_header_prototypes():
-    """tests/test_host_logic.py::test_ctypes_signatures_agree_with_the_header_prototypes, for the second header and table."""
-    C = ctypes
-
-    def klass_of_decl(decl):
-        decl = " ".join(decl.split())
-        if decl == "void":
-            return None
-        if "*" in decl:
-            return "ptr"
-        if re.search(r"\bint64_t\b", decl):
-            return "i64"
-        if re.search(r"\bdouble\b", decl):
-            return "dbl"
-        if re.search(r"\b(int|tsgu_vtype|tsgu_itype)\b", decl):
-            return "int"
-        raise AssertionError(f"unclassified parameter {decl!r}")
-
-    def klass_of_ctype(t):
-        if t in (C.c_void_p, C.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
-            return "ptr"
-        return {C.c_int64: "i64", C.c_int: "int", C.c_double: "dbl"}[t]
-
-    seen = set()
-    for name, params in _prototypes(HEADER):
-        want = [k for k in (klass_of_decl(d) for d in params.split(",")) if k is not None]
-        got = [klass_of_ctype(t) for t in _backend.SIGNATURES_SOFTMAX[name][1]]
-        assert got == want, (name, got, want)
-        seen.add(name)
-    assert seen == set(_backend.SIGNATURES_SOFTMAX)
-    # both launchers end in (device, stream), the convention of tsgu_hip.h
-    for name, params in _prototypes(HEADER)[1:]:
-        assert [" ".join(p.split()) for p in params.split(",")][-2:] == ["int device", "void* stream"], name
-
-
-def test_the_first_header_and_the_abi_version_are_untouched():
-    old = {n for n, _ in _prototypes(os.path.join(ROOT, "include", "tsgu_hip.h"))}
-    assert old == set(_backend.SIGNATURES) and not any("softmax" in n for n in old)
-    assert not set(ENTRIES) & set(_backend.SIGNATURES)
-    assert _backend.load_library().tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    assert "tsgu_hip.h" in open(HEADER).read()
-
-
 def test_range_constant_is_the_kernels():
     src = open(os.path.join(ROOT, "torchsparsegradutils_amd", "csrc", "logsumexp_impl.h")).read()
     assert int(re.search(r"kLseStageBytes\s*=\s*(\d+)", src).group(1)) == _backend.SOFTMAX_STAGE_BYTES
@@ -428,7 +366,6 @@ def test_range_constant_is_the_kernels():
     assert _backend.segment_softmax_range(torch.float64) == 1024
 
 
-OK, BAD_DTYPE, BAD_ARG, TOO_LARGE = 0, -1, -2, -3
 FAKE = 0x7F0000001000          # a 16-byte aligned address that is never dereferenced: every call below is refused on the host
 
 

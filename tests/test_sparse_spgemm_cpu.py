@@ -2,20 +2,15 @@
 CPU, the CPU path of sparse_spgemm for COO and CSR operands, every refusal, and the fifth C-ABI header with its host-side
 refusals."""
 
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
+from _abi_cases import BAD_ARG, BAD_DTYPE, OK, TOO_LARGE
 import _spgemm_ref as sr
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_spgemm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "tsgu_hip_spgemm.h")
 DTYPES = {"float32": torch.float32, "float64": torch.float64, "bfloat16": torch.bfloat16}
 
 
@@ -204,73 +199,6 @@ def test_a_row_of_b_with_a_repeated_column_is_refused():
 
 
 # ---- the fifth header ---------------------------------------------------------------------------------------------------------------
-ENTRIES = ("tsgu_spgemm_bins", "tsgu_spgemm_row_bound", "tsgu_spgemm_symbolic", "tsgu_spgemm_numeric", "tsgu_spgemm_grad_a",
-           "tsgu_spgemm_grad_b")
-LAUNCHERS = ENTRIES[1:]
-
-
-def _prototypes(path):
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return re.findall(r"\b(?:int|int64_t|const char\s*\*|size_t)\s+(tsgu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)
-
-
-def test_the_symbols_are_exported_and_bound():
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    for name in ENTRIES:
-        assert hasattr(raw, name), f"{name} is not exported by libtsgu_hip.so"
-    assert tuple(_backend.SIGNATURES_SPGEMM) == ENTRIES
-    assert [n for n, _ in _prototypes(HEADER)] == list(ENTRIES)
-    lib = _backend.load_library()
-    for name in ENTRIES:
-        assert getattr(lib, name).argtypes == _backend.SIGNATURES_SPGEMM[name][1]
-
-
-def test_ctypes_signatures_agree_with_the_header_prototypes():
-    """tests/test_host_logic.py::test_ctypes_signatures_agree_with_the_header_prototypes, for the fifth header."""
-    C = ctypes
-
-    def klass_of_decl(decl):
-        decl = " ".join(decl.split())
-        if decl == "void":
-            return None
-        if "*" in decl:
-            return "ptr"
-        if re.search(r"\bint64_t\b", decl):
-            return "i64"
-        if re.search(r"\bdouble\b", decl):
-            return "dbl"
-        if re.search(r"\b(int|tsgu_vtype|tsgu_itype)\b", decl):
-            return "int"
-        raise AssertionError(f"unclassified parameter {decl!r}")
-
-    def klass_of_ctype(t):
-        if t in (C.c_void_p, C.c_char_p) or hasattr(t, "_type_") and not isinstance(t._type_, str):
-            return "ptr"
-        return {C.c_int64: "i64", C.c_int: "int", C.c_double: "dbl"}[t]
-
-    seen = set()
-    for name, params in _prototypes(HEADER):
-        want = [k for k in (klass_of_decl(d) for d in params.split(",")) if k is not None]
-        got = [klass_of_ctype(t) for t in _backend.SIGNATURES_SPGEMM[name][1]]
-        assert got == want, (name, got, want)
-        seen.add(name)
-        if name in LAUNCHERS:
-            assert [" ".join(p.split()) for p in params.split(",")][-2:] == ["int device", "void* stream"], name
-    assert seen == set(_backend.SIGNATURES_SPGEMM)
-
-
-def test_the_older_headers_and_the_abi_version_are_untouched():
-    tables = (("tsgu_hip.h", _backend.SIGNATURES), ("tsgu_hip_softmax.h", _backend.SIGNATURES_SOFTMAX),
-              ("tsgu_hip_attention.h", _backend.SIGNATURES_ATTENTION), ("tsgu_hip_mm_reduce.h", _backend.SIGNATURES_MM_REDUCE))
-    for header, table in tables:
-        names = {n for n, _ in _prototypes(os.path.join(ROOT, "include", header))}
-        assert names == set(table), header
-        assert not any("spgemm" in n for n in names) and not set(ENTRIES) & set(table)
-    assert _backend.load_library().tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    assert "TSGU_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "tsgu_hip.h")).read()
-    assert '#include "tsgu_hip.h"' in open(HEADER).read()
-
-
 def test_the_bin_limits_are_the_librarys():
     limits, lanes = _backend.spgemm_bins()
     assert limits == _backend.SPGEMM_BIN_LIMITS and lanes == _backend.SPGEMM_BIN_LANES
@@ -282,7 +210,6 @@ def test_the_bin_limits_are_the_librarys():
     assert limits[-1] * 12 + 256 * 20 <= 64 * 1024
 
 
-OK, BAD_DTYPE, BAD_ARG, TOO_LARGE = 0, -1, -2, -3
 FAKE = 0x7F0000001000          # an aligned address that is never dereferenced: every call below is refused, or has no work, on the host
 
 

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import os
+import sys
 import threading
 from typing import Optional
 
@@ -33,7 +34,7 @@ _int = ctypes.c_int
 _ptr = ctypes.c_void_p
 _dbl = ctypes.c_double
 
-# name -> (restype, argtypes); must list every symbol declared in include/tsgu_hip.h
+# One table per header of include/: name -> (restype, argtypes) of every symbol the header declares.  `ABI` below them is the registry.
 ABI_VERSION = 7          # TSGU_ABI_VERSION of include/tsgu_hip.h this binding was written against
 
 SIGNATURES = {
@@ -241,6 +242,20 @@ SIGNATURES_FSAI = {
     "tsgu_csr_fsai": (_int, [_int, _int, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _int, _int, _ptr]),
 }
 
+# header of include/ -> its table: all that `load_library` binds (a header that is missing here would load with ctypes' default int
+# signatures; tests/test_abi_conformance_cpu.py holds this mapping against the directory)
+ABI = {
+    "tsgu_hip.h": SIGNATURES,
+    "tsgu_hip_softmax.h": SIGNATURES_SOFTMAX,
+    "tsgu_hip_attention.h": SIGNATURES_ATTENTION,
+    "tsgu_hip_mm_reduce.h": SIGNATURES_MM_REDUCE,
+    "tsgu_hip_spgemm.h": SIGNATURES_SPGEMM,
+    "tsgu_hip_bsr.h": SIGNATURES_BSR,
+    "tsgu_hip_bsr_attention.h": SIGNATURES_BSR_ATTENTION,
+    "tsgu_hip_factor.h": SIGNATURES_FACTOR,
+    "tsgu_hip_fsai.h": SIGNATURES_FSAI,
+}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -263,12 +278,11 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in (*SIGNATURES.items(), *SIGNATURES_SOFTMAX.items(), *SIGNATURES_ATTENTION.items(),
-                                  *SIGNATURES_MM_REDUCE.items(), *SIGNATURES_SPGEMM.items(), *SIGNATURES_BSR.items(),
-                                  *SIGNATURES_BSR_ATTENTION.items(), *SIGNATURES_FACTOR.items(), *SIGNATURES_FSAI.items()):
-            fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
-            fn.restype = res
-            fn.argtypes = args
+        for table in ABI.values():
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
+                fn.restype = res
+                fn.argtypes = args
         if lib.tsgu_abi_version() != ABI_VERSION:
             raise HipExtensionMissing("libtsgu_hip.so ABI version mismatch; rebuild the extension")
         _lib = lib
@@ -279,6 +293,15 @@ def check(status: int, what: str) -> None:
     if status != 0:
         msg = load_library().tsgu_status_string(status).decode()
         raise RuntimeError(f"{what} failed: {msg} (tsgu status {status})")
+
+
+def _query(name: str, *args):
+    """A host-only query entry of the library: `name` called with `args` followed by one zeroed slot for each out-parameter its
+    signature has left (`int*` / `int64_t*`).  Returns the slots' values as Python ints; raises through `check` under the name."""
+    fn = getattr(load_library(), name)
+    outs = [t._type_(0) for t in fn.argtypes[len(args):]]
+    check(fn(*args, *map(ctypes.byref, outs)), name)
+    return tuple(int(o.value) for o in outs)
 
 
 def vtype_of(t: torch.Tensor) -> int:
@@ -613,15 +636,11 @@ def lattice_config(lp, mode: int, dtype: torch.dtype, p: int):
 
     if not lattice_rows_fit(mode, dtype, p, lp.kind == 0):
         return None
-    import sys
-
     return _lattice.config_for(lp, mode, _VTYPE[dtype], p, _LATTICE_ELEMENT_BYTES[dtype], lattice_lds_bytes, be=sys.modules[__name__])
 
 
 def lattice_tune(lp, mode: int, dtype: torch.dtype, p: int, time_ms):
     """Measured choice among the best-ranked launch configurations of `lp` for these operands (`_lattice.tune_config`)."""
-    import sys
-
     from . import _lattice
 
     return _lattice.tune_config(lp, mode, _VTYPE[dtype], p, _LATTICE_ELEMENT_BYTES[dtype], lattice_lds_bytes, sys.modules[__name__], time_ms)
@@ -785,10 +804,7 @@ def coo_sddmm(row, col, G, B, alpha: float = 1.0):
 
 def segment_logsumexp_workspace_bytes(dtype: torch.dtype, nnz: int) -> int:
     """Workspace bytes tsgu_segment_logsumexp needs for `nnz` entries of value type `dtype`."""
-    out = ctypes.c_int64(0)
-    check(load_library().tsgu_segment_logsumexp_workspace(_VTYPE[dtype], nnz, ctypes.byref(out)),
-          "tsgu_segment_logsumexp_workspace")
-    return int(out.value)
+    return _query("tsgu_segment_logsumexp_workspace", _VTYPE[dtype], nnz)[0]
 
 
 def segment_logsumexp(ptr, perm, val, out, n_groups: int, nnz: int, include_zeros: bool, axis_len: int,
@@ -834,9 +850,7 @@ def segment_softmax_range(dtype: torch.dtype) -> int:
 
 def segment_softmax_workspace_bytes(dtype: torch.dtype, nnz: int) -> int:
     """Workspace bytes the segmented softmax entries need for `nnz` entries of value type `dtype` when groups cross ranges."""
-    out = ctypes.c_int64(0)
-    check(load_library().tsgu_segment_softmax_workspace(_VTYPE[dtype], nnz, ctypes.byref(out)), "tsgu_segment_softmax_workspace")
-    return int(out.value)
+    return _query("tsgu_segment_softmax_workspace", _VTYPE[dtype], nnz)[0]
 
 
 def _softmax_call(name: str, ptr, perm, operands, n_groups: int, log_form: bool, crossing: bool, out=None):
@@ -882,10 +896,7 @@ def attention_supported(dtype: torch.dtype, heads: int, d: int) -> bool:
 def attention_geometry(dtype: torch.dtype, heads: int, d: int):
     """(entry lanes of a row's lane group, rows per workgroup, entries of one staged slice) of the attention kernels for
     (dtype, heads, d): the sizes at which their walk changes path.  Host only."""
-    ep, rpb, stage = _int(0), _int(0), _int(0)
-    check(load_library().tsgu_csr_attention_geometry(_VTYPE[dtype], int(heads), int(d), ctypes.byref(ep), ctypes.byref(rpb),
-                                                     ctypes.byref(stage)), "tsgu_csr_attention_geometry")
-    return int(ep.value), int(rpb.value), int(stage.value)
+    return _query("tsgu_csr_attention_geometry", _VTYPE[dtype], int(heads), int(d))
 
 
 def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
@@ -895,18 +906,33 @@ def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
     return t if ok else t.clone(memory_format=torch.contiguous_format)
 
 
+def _one_dtype(what: str, arrays, one_d: bool = True):
+    """Operand check of a group of index arrays, or of value arrays: contiguous, of one dtype and (`one_d`) 1-D.  Returns the first."""
+    first = arrays[0]
+    for t in arrays:
+        if (one_d and t.dim() != 1) or t.dtype != first.dtype or not t.is_contiguous():
+            raise RuntimeError(f"the {what} must be contiguous{' 1-D' if one_d else ''} arrays of one dtype")
+    return first
+
+
+def _one_width(what: str, dense, row_major: bool = True):
+    """Operand check of a group of dense operands: 2-D, of one dtype and width and (`row_major`) with unit column stride and rows
+    that do not overlap.  Returns the first."""
+    ref = dense[0]
+    for t in dense:
+        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1) or (row_major and (
+                (t.stride(1) != 1 and t.size(1) > 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)))):
+            raise RuntimeError(f"the {what} must be 2-D{' row-major' if row_major else ''} arrays of one dtype and width")
+    return ref
+
+
 def _attention_walk(walk, bias, *dense):
     ptr, idx, perm = walk
     dev = require_device(ptr, idx, perm, bias, *dense)
-    if idx.dtype != ptr.dtype or (perm is not None and perm.dtype != ptr.dtype):
-        raise RuntimeError("the index arrays of a walk must have one dtype")
-    if not (ptr.is_contiguous() and idx.is_contiguous() and (perm is None or perm.is_contiguous())):
-        raise RuntimeError("ptr, idx and perm must be contiguous")
+    _one_dtype("index arrays of a walk", (ptr, idx) if perm is None else (ptr, idx, perm), one_d=False)
     if bias is not None and (bias.dtype != dense[0].dtype or not bias.is_contiguous() or bias.numel() != idx.numel()):
         raise RuntimeError("the bias must be a contiguous value array of the pattern in the operands' dtype")
-    for t in dense:
-        if t.dim() != 2 or t.dtype != dense[0].dtype or t.size(1) != dense[0].size(1):
-            raise RuntimeError("the dense operands must be 2-D [rows, heads*d] of one dtype and width")
+    _one_width("dense operands [rows, heads*d] of an attention", dense, row_major=False)
     return dev
 
 
@@ -958,23 +984,13 @@ MM_REDUCE_OPS = {"amax": 0, "amin": 1}
 def spmm_reduce_geometry(dtype: torch.dtype, p: int):
     """(rows per workgroup, entries of one staging pass, columns per grid.z slice) of the max / min product kernels for `p` columns
     of value type `dtype` with 16-byte aligned operands: the sizes at which their walk changes path.  Host only."""
-    rpb, stage, width = _int(0), _int(0), _int(0)
-    check(load_library().tsgu_csr_spmm_reduce_geometry(_VTYPE[dtype], int(p), ctypes.byref(rpb), ctypes.byref(stage),
-                                                       ctypes.byref(width)), "tsgu_csr_spmm_reduce_geometry")
-    return int(rpb.value), int(stage.value), int(width.value)
+    return _query("tsgu_csr_spmm_reduce_geometry", _VTYPE[dtype], int(p))
 
 
 def _reduce_operands(index_arrays, val, *dense):
     dev = require_device(*index_arrays, val, *dense)
-    first = index_arrays[0]
-    for t in index_arrays:
-        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
-            raise RuntimeError("the index arrays of a max / min product must be contiguous 1-D arrays of one dtype")
-    ref = dense[0]
-    for t in dense:
-        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1) or (t.stride(1) != 1 and t.size(1) > 1) or (
-                t.size(0) > 1 and t.stride(0) < t.size(1)):
-            raise RuntimeError("the dense operands of a max / min product must be 2-D row-major arrays of one dtype and width")
+    _one_dtype("index arrays of a max / min product", index_arrays)
+    ref = _one_width("dense operands of a max / min product", dense)
     if val is not None and (val.dtype != ref.dtype or val.dim() != 1 or not val.is_contiguous()):
         raise RuntimeError(f"expected A and B to have the same dtype, got {val.dtype} and {ref.dtype}")
     return dev
@@ -1016,23 +1032,13 @@ def csr_spmm_reduce_backward_dense(tptr, tidx, perm, val, arg, G, n_rows: int, n
 def bsr_mm_geometry(dtype: torch.dtype, bh: int, bw: int, p: int):
     """(rows of the result per workgroup, columns of the p per workgroup, summed elements per LDS stage) of the block-sparse product
     kernels for blocks of bh × bw elements of `dtype` against `p` dense columns: the sizes at which their walk changes path.  Host only."""
-    rows, cols, stage = _int(0), _int(0), _int(0)
-    check(load_library().tsgu_bsr_mm_geometry(_VTYPE[dtype], int(bh), int(bw), int(p), ctypes.byref(rows), ctypes.byref(cols),
-                                              ctypes.byref(stage)), "tsgu_bsr_mm_geometry")
-    return int(rows.value), int(cols.value), int(stage.value)
+    return _query("tsgu_bsr_mm_geometry", _VTYPE[dtype], int(bh), int(bw), int(p))
 
 
 def _bsr_operands(index_arrays, val, *dense):
     dev = require_device(*index_arrays, val, *dense)
-    first = index_arrays[0]
-    for t in index_arrays:
-        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
-            raise RuntimeError("the index arrays of a block-sparse product must be contiguous 1-D arrays of one dtype")
-    ref = dense[0]
-    for t in dense:
-        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1) or (t.stride(1) != 1 and t.size(1) > 1) or (
-                t.size(0) > 1 and t.stride(0) < t.size(1)):
-            raise RuntimeError("the dense operands of a block-sparse product must be 2-D row-major arrays of one dtype and width")
+    _one_dtype("index arrays of a block-sparse product", index_arrays)
+    ref = _one_width("dense operands of a block-sparse product", dense)
     if ref.size(1) < 1:
         raise RuntimeError("the block-sparse product needs at least one column")
     if val is not None and (val.dtype != ref.dtype or val.dim() != 3 or not val.is_contiguous()):
@@ -1088,22 +1094,13 @@ def bsr_attention_supported(dtype: torch.dtype, heads: int, d: int, bh: int, bw:
 def bsr_attention_geometry(dtype: torch.dtype, heads: int, d: int, bh: int, bw: int):
     """(rows one workgroup owns, keys of one LDS stage) of the block-sparse attention kernels: the sizes at which their walk
     changes path.  Host only."""
-    rows, stage = _int(0), _int(0)
-    check(load_library().tsgu_bsr_attention_geometry(_VTYPE[dtype], int(heads), int(d), int(bh), int(bw), ctypes.byref(rows),
-                                                     ctypes.byref(stage)), "tsgu_bsr_attention_geometry")
-    return int(rows.value), int(stage.value)
+    return _query("tsgu_bsr_attention_geometry", _VTYPE[dtype], int(heads), int(d), int(bh), int(bw))
 
 
 def _bsr_attention_operands(index_arrays, bias, bh: int, bw: int, *dense):
     dev = require_device(*index_arrays, bias, *dense)
-    first = index_arrays[0]
-    for t in index_arrays:
-        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
-            raise RuntimeError("the index arrays of a block-sparse attention must be contiguous 1-D arrays of one dtype")
-    ref = dense[0]
-    for t in dense:
-        if t.dim() != 2 or t.dtype != ref.dtype or t.size(1) != ref.size(1):
-            raise RuntimeError("the dense operands must be 2-D [rows, heads*d] of one dtype and width")
+    _one_dtype("index arrays of a block-sparse attention", index_arrays)
+    ref = _one_width("dense operands [rows, heads*d] of a block-sparse attention", dense, row_major=False)
     if bias is not None and (bias.dtype != ref.dtype or bias.dim() != 3 or tuple(bias.shape[1:]) != (bh, bw) or not bias.is_contiguous()):
         raise RuntimeError(f"the bias must be a contiguous (nnzb, {bh}, {bw}) array of the dense operands' dtype {ref.dtype}")
     return dev
@@ -1172,19 +1169,11 @@ def spgemm_bins():
 
 
 def _spgemm_indices(*arrays):
-    first = arrays[0]
-    for t in arrays:
-        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
-            raise RuntimeError("the index arrays of a sparse × sparse product must be contiguous 1-D arrays of one dtype")
-    return itype_of(first)
+    return itype_of(_one_dtype("index arrays of a sparse × sparse product", arrays))
 
 
 def _spgemm_values(*arrays):
-    first = arrays[0]
-    for t in arrays:
-        if t.dim() != 1 or t.dtype != first.dtype or not t.is_contiguous():
-            raise RuntimeError("the value arrays of a sparse × sparse product must be contiguous 1-D arrays of one dtype")
-    return vtype_of(first)
+    return vtype_of(_one_dtype("value arrays of a sparse × sparse product", arrays))
 
 
 def spgemm_row_bound(a_crow, a_col, b_crow, n_rows: int, n_inner: int):
@@ -1259,10 +1248,7 @@ SEGMENT_MM_TILE_ROWS = 128      # kImmBM of csrc/indexed_mm_impl.h: the row tile
 
 def segment_mm_grad_b_workspace(dtype: torch.dtype, n: int, n_seg: int, d1: int, d2: int):
     """(chunk rows, launch bound on chunks, workspace bytes) of tsgu_segment_mm_grad_b: functions of the shapes only."""
-    c, mc, b = _i64(0), _i64(0), _i64(0)
-    check(load_library().tsgu_segment_mm_grad_b_workspace(_VTYPE[dtype], n, n_seg, d1, d2, ctypes.byref(c), ctypes.byref(mc),
-                                                           ctypes.byref(b)), "tsgu_segment_mm_grad_b_workspace")
-    return int(c.value), int(mc.value), int(b.value)
+    return _query("tsgu_segment_mm_grad_b_workspace", _VTYPE[dtype], n, n_seg, d1, d2)
 
 
 def _imm_geometry(plan, *tensors) -> torch.device:
@@ -1368,9 +1354,7 @@ FACTOR_DTYPES = (torch.float32, torch.float64)
 def factor_geometry(dtype: torch.dtype):
     """(row_capacity, waves_per_block) of the incomplete factorisations for `dtype`: the entries of a row that are staged in LDS (a
     longer row is built in the output array itself) and the rows a workgroup has in flight."""
-    cap, waves = _int(0), _int(0)
-    check(load_library().tsgu_csr_factor_geometry(_VTYPE[dtype], ctypes.byref(cap), ctypes.byref(waves)), "tsgu_csr_factor_geometry")
-    return cap.value, waves.value
+    return _query("tsgu_csr_factor_geometry", _VTYPE[dtype])
 
 
 def csr_factor(kind: str, ptr, idx, diag_pos, val, n: int, shift: float = 0.0, wg_per_cu: int = 1, out=None):
@@ -1406,9 +1390,7 @@ def csr_factor(kind: str, ptr, idx, diag_pos, val, n: int, shift: float = 0.0, w
 def fsai_geometry(dtype: torch.dtype):
     """(row_capacity, rows_per_block) of the FSAI build for `dtype`: the longest row of the pattern S (the largest local system)
     the kernel accepts, and the rows a workgroup takes at a time."""
-    cap, rows = _int(0), _int(0)
-    check(load_library().tsgu_csr_fsai_geometry(_VTYPE[dtype], ctypes.byref(cap), ctypes.byref(rows)), "tsgu_csr_fsai_geometry")
-    return cap.value, rows.value
+    return _query("tsgu_csr_fsai_geometry", _VTYPE[dtype])
 
 
 def csr_fsai(a_ptr, a_idx, a_val, s_ptr, s_idx, n: int, order=None, wg_per_cu: int = 8):

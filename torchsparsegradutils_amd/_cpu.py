@@ -45,10 +45,6 @@ def _cpu_only(*tensors) -> None:
             raise RuntimeError("torchsparsegradutils_amd._cpu was handed a GPU tensor: the torch-op path serves CPU operands only")
 
 
-def _flat(plan: _pt.RowGather) -> _pt.RowGather:
-    return _pt.flat_of(plan) if plan.batch is not None else plan
-
-
 def _values_in_plan_order(plan: _pt.RowGather, values: torch.Tensor) -> torch.Tensor:
     v = values.reshape(-1)
     return v if plan.perm is None else v.index_select(0, plan.perm.reshape(-1).to(torch.int64))
@@ -57,7 +53,7 @@ def _values_in_plan_order(plan: _pt.RowGather, values: torch.Tensor) -> torch.Te
 def matrix(plan: _pt.RowGather, values: torch.Tensor) -> torch.Tensor:
     """The 2-D torch CSR tensor of (plan, values): A's own index arrays (int32 stays int32), block diagonal for a batched plan —
     what the reference assembles with ``sparse_block_diag`` for every batched input (sparse_matmul.py:151-153)."""
-    f = _flat(plan)
+    f = _pt.flat_of(plan)
     return torch.sparse_csr_tensor(f.crow, f.col, _values_in_plan_order(f, values), (f.n_rows, f.n_cols))
 
 
@@ -73,7 +69,7 @@ def sddmm(plan: _pt.RowGather, G: torch.Tensor, B: torch.Tensor, alpha: float = 
     """alpha·<G[row k], B[col k]> (roles swapped: <B[row k], G[col k]>) at the plan's entries, in plan order, shaped like the
     plan's column array (reference sparse_matmul.py:186-205, sparse_solve.py:216-235)."""
     _cpu_only(G, B, plan.crow)
-    f = _flat(plan)
+    f = _pt.flat_of(plan)
     p = G.size(-1)
     row_side = (B if swap_roles else G).reshape(-1, p)
     col_side = (G if swap_roles else B).reshape(-1, p)

@@ -32,11 +32,6 @@ _DTYPES = (torch.float32, torch.float64, torch.bfloat16)
 LIMITS = _be.BSR_ATTENTION_LIMITS
 
 
-def _flat(plan: _pt.RowGather) -> _pt.RowGather:
-    """The 2-D block pattern the kernels walk: the block-diagonal form of a batched operand."""
-    return _pt.flat_of(plan) if plan.batch is not None else plan
-
-
 class SparseBSRAttention(torch.autograd.Function):
     """Autograd kernel behind :func:`sparse_bsr_attention` (once differentiable).  The gradient of ``A`` is a BSR tensor on A's own
     ``crow_indices()`` / ``col_indices()`` tensors with A's index dtype."""
@@ -45,7 +40,7 @@ class SparseBSRAttention(torch.autograd.Function):
     def forward(ctx, A, Q, K, V, heads, scale, use_bias):
         A = A.detach()
         plan = _pt.from_bsr(A)
-        flat = _flat(plan)
+        flat = _pt.flat_of(plan)
         values = A.values()
         bh, bw = values.shape[-2:]
         d = Q.size(-1)
@@ -68,7 +63,7 @@ class SparseBSRAttention(torch.autograd.Function):
     def backward(ctx, dO):  # type: ignore[override]
         Q2, K2, V2, O, keep, bias = ctx.saved_tensors
         plan: _pt.RowGather = ctx.plan
-        flat = _flat(plan)
+        flat = _pt.flat_of(plan)
         heads, scale = ctx.heads, ctx.scale
         bh, bw = ctx.values_shape[-2:]
         want_dA = ctx.needs_input_grad[0] and ctx.use_bias

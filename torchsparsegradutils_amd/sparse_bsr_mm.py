@@ -27,11 +27,6 @@ __all__ = ["sparse_bsr_mm", "SparseBSRMatMul"]
 _DTYPES = (torch.float32, torch.float64, torch.bfloat16)
 
 
-def _flat(plan: _pt.RowGather) -> _pt.RowGather:
-    """The 2-D block pattern the kernels walk: the block-diagonal form of a batched operand."""
-    return _pt.flat_of(plan) if plan.batch is not None else plan
-
-
 class SparseBSRMatMul(torch.autograd.Function):
     """Autograd kernel behind :func:`sparse_bsr_mm` (once differentiable).  The gradient of ``A`` is a BSR tensor on A's own
     ``crow_indices()`` / ``col_indices()`` tensors with A's index dtype."""
@@ -41,7 +36,7 @@ class SparseBSRMatMul(torch.autograd.Function):
         grad_flag = A.requires_grad or B.requires_grad
         A, B = A.detach(), B.detach()
         plan = _pt.from_bsr(A)
-        flat = _flat(plan)
+        flat = _pt.flat_of(plan)
         values = A.values()
         bh, bw = values.shape[-2:]
         p = B.size(-1)
@@ -62,7 +57,7 @@ class SparseBSRMatMul(torch.autograd.Function):
     def backward(ctx, grad):  # type: ignore[override]
         blocks, Bk = ctx.saved_tensors
         plan: _pt.RowGather = ctx.plan
-        flat = _flat(plan)
+        flat = _pt.flat_of(plan)
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         G = _be.rowmajor(grad.reshape(-1, grad.size(-1)))
         bh, bw = blocks.shape[-2:]

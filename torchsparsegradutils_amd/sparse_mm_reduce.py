@@ -35,11 +35,6 @@ REDUCTIONS = ("sum", "mean", "amax", "amin")
 _DTYPES = (torch.float32, torch.float64, torch.bfloat16)
 
 
-def _flat(plan: _pt.RowGather) -> _pt.RowGather:
-    """The 2-D pattern the kernels walk: the block-diagonal form of a batched CSR operand (batched COO arrives flattened)."""
-    return _pt.flat_of(plan) if plan.batch is not None else plan
-
-
 class SparseMMReduce(torch.autograd.Function):
     """Autograd kernel behind :func:`sparse_mm_reduce` for ``amax`` and ``amin`` (once differentiable).  ``A`` is CSR or coalesced
     COO; the gradient of ``A`` has A's layout, index tensors and index dtype."""
@@ -49,7 +44,7 @@ class SparseMMReduce(torch.autograd.Function):
         grad_flag = A.requires_grad or B.requires_grad
         A, B = A.detach(), B.detach()
         op = _Operand(A)
-        flat = _flat(op.plan)
+        flat = _pt.flat_of(op.plan)
         p = B.size(-1)
         values = op.values.reshape(-1).contiguous()
         Bk = _be.rowmajor(B.reshape(-1, p))
@@ -69,7 +64,7 @@ class SparseMMReduce(torch.autograd.Function):
     def backward(ctx, grad):  # type: ignore[override]
         values, Bk, arg = ctx.saved_tensors
         op: _Operand = ctx.op
-        flat = _flat(op.plan)
+        flat = _pt.flat_of(op.plan)
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         G = _be.rowmajor(grad.reshape(-1, grad.size(-1)))
         crow, col = flat.crow.contiguous(), flat.col.contiguous()
