@@ -3,7 +3,7 @@
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
-``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` beside them;
+``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_lobpcg`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -16,6 +16,7 @@ from .sparse_bsr_attention import SparseBSRAttention, sparse_bsr_attention
 from .sparse_bsr_mm import SparseBSRMatMul, sparse_bsr_mm
 from .sparse_factor import SparseIC0, SparseILU0, sparse_ic0, sparse_ilu0
 from .sparse_fsai import SparseFSAI, sparse_fsai
+from .sparse_lobpcg import SparseLOBPCG, sparse_lobpcg
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
@@ -41,6 +42,8 @@ __all__ = [
     "SparseIC0",
     "sparse_fsai",
     "SparseFSAI",
+    "sparse_lobpcg",
+    "SparseLOBPCG",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",

@@ -256,6 +256,19 @@ ABI = {
     "tsgu_hip_fsai.h": SIGNATURES_FSAI,
 }
 
+# the additive entries of csrc/tsgu_hip_lobpcg.h (same library, same ABI version): a STAGED header, declared beside the sources
+# until it moves to include/ ("Adding a header")
+SIGNATURES_LOBPCG = {
+    "tsgu_tall_geometry": (_int, [_int, _i64, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_i64)]),
+    "tsgu_tall_gram": (_int, [_int, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _int, _int, _ptr]),
+    "tsgu_tall_combine": (_int, [_int, _i64, _int, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_lobpcg_residual": (_int, [_int, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _int, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after `ABI` (tests/test_sparse_lobpcg_cpu.py holds it against the header)
+STAGED = {"tsgu_hip_lobpcg.h": SIGNATURES_LOBPCG}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -278,7 +291,7 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for table in ABI.values():
+        for table in (*ABI.values(), *STAGED.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1417,6 +1430,96 @@ def csr_fsai(a_ptr, a_idx, a_val, s_ptr, s_idx, n: int, order=None, wg_per_cu: i
     launch("tsgu_csr_fsai", dev, vtype_of(a_val), itype_of(a_ptr), n, a_ptr, a_idx, a_val, s_ptr, s_idx, s_idx.numel(), order, out, info,
            int(wg_per_cu))
     return out, info
+
+
+def tall_geometry(dtype: torch.dtype, n: int = 0, a: int = 0, b: int = 0):
+    """(kmax, wmax, rows_per_workgroup, workspace_bytes) of the tall-skinny kernels (csrc/tsgu_hip_lobpcg.h): the widest block, the
+    widest operand of the Gram kernel, the rows of a chunk, and the bytes `tall_gram` needs for `n` rows and an `a` x `b` result
+    (`lobpcg_residual`: a = k, b = 1)."""
+    return _query("tsgu_tall_geometry", _VTYPE[dtype], int(n), int(a), int(b))
+
+
+def _tall_views(what: str, views):
+    """Operand check of the dense views of a tall-skinny call: 2-D, one dtype and height, unit column stride, rows that do not overlap."""
+    ref = views[0]
+    if ref.dtype not in FACTOR_DTYPES:
+        raise TypeError(f"{what}: float32 and float64 operands only, got {ref.dtype}")
+    for t in views:
+        if t.dim() != 2 or t.dtype != ref.dtype or t.size(0) != ref.size(0) or (t.stride(1) != 1 and t.size(1) > 1) or \
+                (t.size(0) > 1 and t.stride(0) < t.size(1)):
+            raise RuntimeError(f"the {what} must be 2-D row-major views of one dtype and height")
+    return ref
+
+
+def _tall_workspace(ref: torch.Tensor, a: int, b: int, workspace=None) -> torch.Tensor:
+    need = tall_geometry(ref.dtype, ref.size(0), a, b)[3]
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need // ref.element_size(), 1), dtype=ref.dtype, device=ref.device)
+    return workspace
+
+
+def tall_gram(Y, Z, out=None, workspace=None, workgroups: int = 0):
+    """YᵀZ (a, b) for the row-major views Y (n, a) and Z (n, b), a, b <= wmax; `Y is Z` is read once.  Deterministic: the same bits
+    for every `workgroups` (0: the library's choice).  `workspace`: scratch of `tall_geometry(...)[3]` bytes, allocated when missing."""
+    ref = _tall_views("operands of tall_gram", (Y, Z))
+    dev = require_device(Y, Z, out, workspace)
+    a, b = Y.size(1), Z.size(1)
+    if out is None:
+        out = torch.empty((a, b), dtype=ref.dtype, device=dev)
+    elif out.shape != (a, b) or out.dtype != ref.dtype or (b > 1 and out.stride(1) != 1):
+        raise RuntimeError(f"tall_gram: out must be a row-major ({a}, {b}) array of {ref.dtype}")
+    workspace = _tall_workspace(ref, a, b, workspace)
+    launch("tsgu_tall_gram", dev, vtype_of(ref), ref.size(0), a, b, Y, _ld(Y), Z, _ld(Z), out, _ld(out), workspace,
+           workspace.numel() * workspace.element_size(), int(workgroups))
+    return out
+
+
+def tall_combine(inputs, outputs, coefs, betas=None, workgroups: int = 0):
+    """outputs[t] = betas[t]·outputs[t] + Σ_i inputs[i] @ coefs[t][i] in one pass over the rows: up to six (n, <= kmax) input views,
+    up to four output views, `coefs[t][i]` a (width of input i, width of output t) matrix or None (the block does not
+    contribute).  No output may share an element with an input or another output (views that interleave in one allocation do
+    not); the library refuses anything else.  Returns `outputs`."""
+    ref = _tall_views("operands of tall_combine", (*inputs, *outputs))
+    dev = require_device(*inputs, *outputs, *(c for row in coefs for c in row))
+    n_in, n_out = len(inputs), len(outputs)
+    if len(coefs) != n_out or any(len(row) != n_in for row in coefs):
+        raise RuntimeError(f"tall_combine: {n_out} outputs and {n_in} inputs need {n_out} rows of {n_in} coefficient matrices")
+    flat = []
+    for t, row in enumerate(coefs):
+        for i, c in enumerate(row):
+            if c is not None and (c.dtype != ref.dtype or tuple(c.shape) != (inputs[i].size(1), outputs[t].size(1))):
+                raise RuntimeError(f"tall_combine: coefficient ({t}, {i}) must be a ({inputs[i].size(1)}, {outputs[t].size(1)}) "
+                                   f"matrix of {ref.dtype}")
+            if c is not None and ((c.size(1) > 1 and c.stride(1) != 1) or (c.size(0) > 1 and c.stride(0) < c.size(1))):
+                c = c.contiguous()           # (a column-major result of torch.linalg: the kernel reads row-major matrices)
+            flat.append(c)
+    ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[_p(t) for t in ts])      # noqa: E731
+    ints = lambda xs: (ctypes.c_int64 * len(xs))(*xs)                         # noqa: E731
+    host = [ptrs(inputs), ints([t.size(1) for t in inputs]), ints([_ld(t) for t in inputs]),
+            ptrs(outputs), ints([t.size(1) for t in outputs]), ints([_ld(t) for t in outputs]),
+            (ctypes.c_double * n_out)(*([0.0] * n_out if betas is None else [float(x) for x in betas])),
+            ptrs(flat), ints([0 if c is None else _ld(c) for c in flat])]
+    addr = [ctypes.addressof(h) for h in host]
+    launch("tsgu_tall_combine", dev, vtype_of(ref), ref.size(0), n_in, addr[0], addr[1], addr[2], n_out, addr[3], addr[4], addr[5],
+           addr[6], addr[7], addr[8], int(workgroups))
+    return outputs
+
+
+def lobpcg_residual(AX, X, lam, out=None, workspace=None, workgroups: int = 0):
+    """(R, sumsq): R = AX − X·diag(lam) for (n, k <= kmax) views and a device vector `lam` (k,), and the column sums of squares of R
+    (k,) — deterministic, as `tall_gram`.  `out` receives R (it may share no element with AX or X)."""
+    ref = _tall_views("operands of lobpcg_residual", (AX, X) if out is None else (AX, X, out))
+    dev = require_device(AX, X, lam, out, workspace)
+    k = AX.size(1)
+    if X.size(1) != k or lam.shape != (k,) or lam.dtype != ref.dtype or not lam.is_contiguous() or (out is not None and out.size(1) != k):
+        raise RuntimeError(f"lobpcg_residual: AX, X and R must be (n, {k}) views and lam a contiguous ({k},) vector of {ref.dtype}")
+    if out is None:
+        out = torch.empty((ref.size(0), k), dtype=ref.dtype, device=dev)
+    sumsq = torch.empty(k, dtype=ref.dtype, device=dev)
+    workspace = _tall_workspace(ref, k, 1, workspace)
+    launch("tsgu_lobpcg_residual", dev, vtype_of(ref), ref.size(0), k, AX, _ld(AX), X, _ld(X), lam, out, _ld(out), sumsq, workspace,
+           workspace.numel() * workspace.element_size(), int(workgroups))
+    return out, sumsq
 
 
 _PENDING = []            # (event or None, pinned / host int32 slot, what, tsgu status)

@@ -577,3 +577,52 @@ def csr_fsai(a_crow: torch.Tensor, a_col: torch.Tensor, a_val: torch.Tensor, s_c
             bad = bad or i + 1
         out[sptr[i]:sptr[i + 1]] = g
     return torch.from_numpy(out), torch.tensor(bad, dtype=torch.int64)
+
+
+# ---- the three primitives of the LOBPCG loop (utils/lobpcg.py): csrc/tsgu_hip_lobpcg.h in torch ops -------------------------------
+
+def tall_gram(Y: torch.Tensor, Z: torch.Tensor, out=None, workspace=None, workgroups: int = 0) -> torch.Tensor:
+    """YᵀZ for (n, a) and (n, b) views."""
+    _cpu_only(Y, Z, out)
+    return torch.matmul(Y.t(), Z) if out is None else torch.matmul(Y.t(), Z, out=out)
+
+
+def _views_meet(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Do two row-major (n, w) views share an element?  The kernel's rule (csrc/lobpcg_impl.h, tall_views_meet): views that
+    interleave in one allocation (equal row strides, disjoint column windows) do not, any other overlap of the address ranges does."""
+    size = a.element_size()
+    lda, ldb = (t.stride(0) if t.size(0) > 1 else t.size(1) for t in (a, b))
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    a1, b1 = a0 + ((a.size(0) - 1) * lda + a.size(1)) * size, b0 + ((b.size(0) - 1) * ldb + b.size(1)) * size
+    if a1 <= b0 or b1 <= a0:
+        return False
+    if lda != ldb or (b0 - a0) % size:
+        return True
+    d = ((b0 - a0) // size) % lda
+    return not (d >= a.size(1) and d + b.size(1) <= lda)
+
+
+def tall_combine(inputs, outputs, coefs, betas=None, workgroups: int = 0):
+    """outputs[t] = betas[t]·outputs[t] + Σ_i inputs[i] @ coefs[t][i]; a None coefficient does not contribute.  The same refusal
+    as the kernel's: an output shares no element with an input or with another output."""
+    _cpu_only(*inputs, *outputs)
+    for t, o in enumerate(outputs):
+        if any(_views_meet(o, s) for s in inputs) or any(_views_meet(o, q) for q in outputs[:t]):
+            raise RuntimeError("tall_combine: an output may share no element with an input or another output")
+    for t, out in enumerate(outputs):
+        beta = 0.0 if betas is None else float(betas[t])
+        acc = out * beta if beta != 0.0 else torch.zeros_like(out)
+        for s, c in zip(inputs, coefs[t]):
+            if c is not None:
+                acc = acc + s @ c
+        out.copy_(acc)
+    return outputs
+
+
+def lobpcg_residual(AX: torch.Tensor, X: torch.Tensor, lam: torch.Tensor, out=None, workspace=None, workgroups: int = 0):
+    """(R = AX − X·diag(lam), the column sums of squares of R)."""
+    _cpu_only(AX, X, lam, out)
+    R = AX - X * lam
+    if out is not None:
+        R = out.copy_(R)
+    return R, (R * R).sum(dim=0)

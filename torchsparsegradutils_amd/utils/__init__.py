@@ -8,6 +8,8 @@ from .linear_cg import linear_cg, LinearCGSettings
 from .minres import minres, MINRESSettings
 from .bicgstab import bicgstab, BICGSTABSettings
 from .lsmr import lsmr
+# the eigensolver loop on the tall-skinny kernels (csrc/lobpcg.hip)
+from .lobpcg import lobpcg
 
 # COO/CSR conversion and batching glue
 from .utils import convert_coo_to_csr, convert_coo_to_csr_indices_values
