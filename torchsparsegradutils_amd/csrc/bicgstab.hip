@@ -115,36 +115,29 @@ __global__ __launch_bounds__(kBlock) void bicg_update_p_kernel(int64_t n, int64_
                                                                const V* __restrict__ v, const V* __restrict__ scal,
                                                                const int* __restrict__ flags, int lpr, int rpp) {
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    if (!(rs < rpp && c < p)) return;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
+    if (!L.on) return;
     V beta[VEC], bo[VEC];
     bool act[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-        act[k] = flags[2 + c + k] == 0;
-        beta[k] = scal[5 * p + c + k];
-        bo[k] = beta[k] * scal[2 * p + c + k];
+        act[k] = flags[2 + L.c + k] == 0;
+        beta[k] = scal[5 * p + L.c + k];
+        bo[k] = beta[k] * scal[2 * p + L.c + k];
     }
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V pp[VEC], rr[VEC], vv[VEC];
+        load_vec<V, VEC>(pv + o, pp);
+        load_vec<V, VEC>(r + o, rr);
+        load_vec<V, VEC>(v + o, vv);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (row < n) {
-            const int64_t o = row * p + c;
-            V pp[VEC], rr[VEC], vv[VEC];
-            load_vec<V, VEC>(pv + o, pp);
-            load_vec<V, VEC>(r + o, rr);
-            load_vec<V, VEC>(v + o, vv);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const V nw = (pp[k] * beta[k] - bo[k] * vv[k]) + rr[k];
-                pp[k] = act[k] ? nw : pp[k];
-            }
-            store_vec<V, VEC>(pv + o, pp);
+        for (int k = 0; k < VEC; ++k) {
+            const V nw = (pp[k] * beta[k] - bo[k] * vv[k]) + rr[k];
+            pp[k] = act[k] ? nw : pp[k];
         }
-    }
+        store_vec<V, VEC>(pv + o, pp);
+    });
 }
 
 // s = r - alpha*v ; partial |s|^2      (bicgstab.py:200-203)
@@ -155,47 +148,30 @@ __global__ __launch_bounds__(kBlock) void bicg_update_s_kernel(int64_t n, int64_
                                                                V* __restrict__ partial) {
     __shared__ V red[kBlock * VEC];
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool on = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     V alpha[VEC], acc[VEC];
     bool act[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
         acc[k] = 0;
-        act[k] = on && flags[2 + c + k] == 0;
-        alpha[k] = on ? scal[p + c + k] : (V)0;
+        act[k] = L.on && flags[2 + L.c + k] == 0;
+        alpha[k] = L.on ? scal[p + L.c + k] : (V)0;
     }
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V ss[VEC], rr[VEC], vv[VEC];
+        load_vec<V, VEC>(s + o, ss);
+        load_vec<V, VEC>(r + o, rr);
+        load_vec<V, VEC>(v + o, vv);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (on && row < n) {
-            const int64_t o = row * p + c;
-            V ss[VEC], rr[VEC], vv[VEC];
-            load_vec<V, VEC>(s + o, ss);
-            load_vec<V, VEC>(r + o, rr);
-            load_vec<V, VEC>(v + o, vv);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const V nw = rr[k] - alpha[k] * vv[k];
-                ss[k] = act[k] ? nw : ss[k];
-                acc[k] = fma(ss[k], ss[k], acc[k]);
-            }
-            store_vec<V, VEC>(s + o, ss);
+        for (int k = 0; k < VEC; ++k) {
+            const V nw = rr[k] - alpha[k] * vv[k];
+            ss[k] = act[k] ? nw : ss[k];
+            acc[k] = fma(ss[k], ss[k], acc[k]);
         }
-    }
-    if (rs < rpp) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[(rs * lpr + cl) * VEC + k] = acc[k];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V sum = 0;
-        for (int k = 0; k < rpp; ++k) sum += red[k * lpr * VEC + cc];
-        partial[(int64_t)blockIdx.x * p + cc] = sum;
-    }
+        store_vec<V, VEC>(s + o, ss);
+    });
+    fold_partial_row<V, VEC>(red, acc, L, p, partial + (int64_t)blockIdx.x * p);
 }
 
 // partial <t,s>, <t,t>, <r0,t>      (bicgstab.py:223-224); sets are `set_stride` elements apart
@@ -205,42 +181,28 @@ __global__ __launch_bounds__(kBlock) void bicg_dots3_kernel(int64_t n, int64_t p
                                                             int rpp, V* __restrict__ partial, int64_t set_stride) {
     __shared__ V red[kBlock * VEC];
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool on = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     V a0[VEC], a1[VEC], a2[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) a0[k] = a1[k] = a2[k] = 0;
-    const int64_t rb = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V tt[VEC], ss[VEC], rr[VEC];
+        load_vec<V, VEC>(tv + o, tt);
+        load_vec<V, VEC>(s + o, ss);
+        load_vec<V, VEC>(r0v + o, rr);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = rb + (int64_t)ps * rpp + rs;
-        if (on && row < n) {
-            const int64_t o = row * p + c;
-            V tt[VEC], ss[VEC], rr[VEC];
-            load_vec<V, VEC>(tv + o, tt);
-            load_vec<V, VEC>(s + o, ss);
-            load_vec<V, VEC>(r0v + o, rr);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                a0[k] = fma(tt[k], ss[k], a0[k]);
-                a1[k] = fma(tt[k], tt[k], a1[k]);
-                a2[k] = fma(rr[k], tt[k], a2[k]);
-            }
+        for (int k = 0; k < VEC; ++k) {
+            a0[k] = fma(tt[k], ss[k], a0[k]);
+            a1[k] = fma(tt[k], tt[k], a1[k]);
+            a2[k] = fma(rr[k], tt[k], a2[k]);
         }
-    }
+    });
     for (int set = 0; set < 3; ++set) {
-        if (rs < rpp) {
+        V a[VEC];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) red[(rs * lpr + cl) * VEC + k] = set == 0 ? a0[k] : set == 1 ? a1[k] : a2[k];
-        }
-        __syncthreads();
-        for (int64_t cc = t; cc < p; cc += kBlock) {
-            V sum = 0;
-            for (int k = 0; k < rpp; ++k) sum += red[k * lpr * VEC + cc];
-            partial[set * set_stride + (int64_t)blockIdx.x * p + cc] = sum;
-        }
+        for (int k = 0; k < VEC; ++k) a[k] = set == 0 ? a0[k] : set == 1 ? a1[k] : a2[k];
+        fold_partial_row<V, VEC>(red, a, L, p, partial + set * set_stride + (int64_t)blockIdx.x * p);
         __syncthreads();
     }
 }
@@ -256,58 +218,49 @@ __global__ __launch_bounds__(kBlock) void bicg_update_x_kernel(int64_t n, int64_
                                                                V* __restrict__ partial, const V* __restrict__ zv) {
     __shared__ V red[kBlock * VEC];
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool on = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
+    // This kernel's selects are sensitive to how the code around them is written (seen in the gfx950 assembly): with the pass body
+    // in a functor for for_rows() the compiler turns them into branches per column and the wide-lane instances lose their packed
+    // multiplies and adds; with L.on read from the lane value they get seven more exec-mask regions.  So the pass loop is written
+    // out here and `on` is formed here (the same expression as L.on).
+    const bool on = L.rs < rpp && L.c < p;
     V alpha[VEC], omega[VEC], acc[VEC];
     bool act[VEC], hf[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
         acc[k] = 0;
-        const bool f = on ? flags[2 + c + k] != 0 : true;
-        hf[k] = on && !f && flags[2 + p + c + k] != 0;
+        const bool f = on ? flags[2 + L.c + k] != 0 : true;
+        hf[k] = on && !f && flags[2 + p + L.c + k] != 0;
         act[k] = on && !f && !hf[k];
-        alpha[k] = on ? scal[p + c + k] : (V)0;
-        omega[k] = on ? scal[2 * p + c + k] : (V)0;
+        alpha[k] = on ? scal[p + L.c + k] : (V)0;
+        omega[k] = on ? scal[2 * p + L.c + k] : (V)0;
     }
-    const int64_t rb = (int64_t)blockIdx.x * rpp * kPasses;
 #pragma unroll
     for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = rb + (int64_t)ps * rpp + rs;
-        if (on && row < n) {
-            const int64_t o = row * p + c;
-            V xx[VEC], rr[VEC], ss[VEC], tt[VEC], pp[VEC], zz[VEC];
-            load_vec<V, VEC>(x + o, xx);
-            load_vec<V, VEC>(r + o, rr);
-            load_vec<V, VEC>(s + o, ss);
-            load_vec<V, VEC>(tv + o, tt);
-            load_vec<V, VEC>(pv + o, pp);
-            if constexpr (PRE) load_vec<V, VEC>(zv + o, zz);
+        const int64_t row = L.r0 + (int64_t)ps * L.rpp + L.rs;
+        if (!(on && row < n)) continue;
+        const int64_t o = row * p + L.c;
+        V xx[VEC], rr[VEC], ss[VEC], tt[VEC], pp[VEC], zz[VEC];
+        load_vec<V, VEC>(x + o, xx);
+        load_vec<V, VEC>(r + o, rr);
+        load_vec<V, VEC>(s + o, ss);
+        load_vec<V, VEC>(tv + o, tt);
+        load_vec<V, VEC>(pv + o, pp);
+        if constexpr (PRE) load_vec<V, VEC>(zv + o, zz);
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const V ap = alpha[k] * pp[k];
-                const V xh = xx[k] + ap;
-                const V xa = (xx[k] + omega[k] * (PRE ? zz[k] : ss[k])) + ap;
-                const V rn = ss[k] - omega[k] * tt[k];
-                xx[k] = hf[k] ? xh : (act[k] ? xa : xx[k]);
-                rr[k] = act[k] ? rn : rr[k];
-                acc[k] = fma(rr[k], rr[k], acc[k]);
-            }
-            store_vec<V, VEC>(x + o, xx);
-            store_vec<V, VEC>(r + o, rr);
+        for (int k = 0; k < VEC; ++k) {
+            const V ap = alpha[k] * pp[k];
+            const V xh = xx[k] + ap;
+            const V xa = (xx[k] + omega[k] * (PRE ? zz[k] : ss[k])) + ap;
+            const V rn = ss[k] - omega[k] * tt[k];
+            xx[k] = hf[k] ? xh : (act[k] ? xa : xx[k]);
+            rr[k] = act[k] ? rn : rr[k];
+            acc[k] = fma(rr[k], rr[k], acc[k]);
         }
+        store_vec<V, VEC>(x + o, xx);
+        store_vec<V, VEC>(r + o, rr);
     }
-    if (rs < rpp) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[(rs * lpr + cl) * VEC + k] = acc[k];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V sum = 0;
-        for (int k = 0; k < rpp; ++k) sum += red[k * lpr * VEC + cc];
-        partial[(int64_t)blockIdx.x * p + cc] = sum;
-    }
+    fold_partial_row<V, VEC>(red, acc, L, p, partial + (int64_t)blockIdx.x * p);
 }
 
 }  // namespace tsgu

@@ -14,35 +14,18 @@ __global__ __launch_bounds__(kBlock) void coldot_partial_kernel(int64_t n, int64
                                                                 const V* __restrict__ Y, int64_t ldy, int lpr, int rpp,
                                                                 V* __restrict__ partial) {
     __shared__ V red[kBlock * VEC];
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool act = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     V acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0;
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t r) {
+        V x[VEC], y[VEC];
+        load_vec<V, VEC>(X + r * ldx + L.c, x);
+        load_vec<V, VEC>(Y + r * ldy + L.c, y);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t r = r0 + (int64_t)ps * rpp + rs;
-        if (act && r < n) {
-            V x[VEC], y[VEC];
-            load_vec<V, VEC>(X + r * ldx + c, x);
-            load_vec<V, VEC>(Y + r * ldy + c, y);
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = fma(x[v], y[v], acc[v]);
-        }
-    }
-    if (rs < rpp) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) red[(rs * lpr + cl) * VEC + v] = acc[v];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V s = 0;
-        for (int k = 0; k < rpp; ++k) s += red[k * lpr * VEC + cc];
-        partial[(int64_t)blockIdx.x * p + cc] = s;
-    }
+        for (int v = 0; v < VEC; ++v) acc[v] = fma(x[v], y[v], acc[v]);
+    });
+    fold_partial_row<V, VEC>(red, acc, L, p, partial + (int64_t)blockIdx.x * p);
 }
 
 template <typename V>
@@ -56,6 +39,44 @@ __global__ __launch_bounds__(kBlock) void colsum_finalize_kernel(const V* __rest
 }
 
 // ---- CG ---------------------------------------------------------------------------------
+// The per-column scalars of an iteration, written once for the four-step and the two-launch form (which keep their own state layouts).
+
+// alpha = <r,z> / pᵀAp by safe division (linear_cg.py:67-71); a converged column is frozen (:74)
+template <typename V>
+__device__ __forceinline__ V cg_safe_alpha(V rr, V pap, V eps, bool converged) {
+    V alpha = pap < eps ? (V)0 : rr / pap;
+    if (converged) alpha = 0;
+    return alpha;
+}
+
+template <typename V>
+struct CgColumn {
+    V beta, norm;
+    int has_converged;
+};
+
+// beta = <r,z>_new / <r,z>_old with the reference's safe division (linear_cg.py:35-43); the residual norm and what follows from it
+template <typename V>
+__device__ __forceinline__ CgColumn<V> cg_beta_norm(V ip_new, V ip_old, V rr_new, V eps, bool rhs_is_zero, V stop_after) {
+    CgColumn<V> col;
+    col.beta = ip_old < eps ? (V)0 : ip_new / ip_old;
+    col.norm = sqrt(rr_new);                            // ‖r‖₂ (linear_cg.py:372)
+    if (rhs_is_zero) col.norm = 0;                      // rhs_is_zero mask (:373)
+    col.has_converged = col.norm < stop_after ? 1 : 0;  // has_converged (:374)
+    return col;
+}
+
+// stop rule (linear_cg.py:376-382): k >= min(10, max_iter-1) and mean‖r‖ < tol.  normsum: the sums of the norms thread t < 64 saw
+// (columns t, t + 64, ...), added here in thread order; called by one thread, after a barrier.
+template <typename V>
+__device__ __forceinline__ bool cg_mean_norm_stops(const V* normsum, int64_t p, int it, int min_iter_index, V tolerance) {
+    V s = 0;
+    const int lim = p < 64 ? (int)p : 64;
+    for (int k = 0; k < lim; ++k) s += normsum[k];
+    const V mean = s / (V)p;
+    return it >= min_iter_index && mean < tolerance;
+}
+
 // scal: [rr | alpha | beta | rnorm] each [p];  flags: [done, iters, has_converged[p], rhs_is_zero[p]]
 template <typename V>
 __global__ __launch_bounds__(kBlock) void cg_alpha_kernel(const V* __restrict__ pap_partial, int64_t n_partial, int64_t p,
@@ -67,10 +88,7 @@ __global__ __launch_bounds__(kBlock) void cg_alpha_kernel(const V* __restrict__ 
     const V pap = block_colsum<V>(pap_partial, n_partial, p, c0, w, red);
     if ((int)threadIdx.x < w) {
         const int64_t c = c0 + threadIdx.x;
-        // safe division (linear_cg.py:67-71) then freeze converged columns (:74)
-        V alpha = pap < eps ? (V)0 : scal[c] / pap;
-        if (flags[2 + c] != 0) alpha = 0;
-        scal[p + c] = alpha;
+        scal[p + c] = cg_safe_alpha(scal[c], pap, eps, flags[2 + c] != 0);
     }
 }
 
@@ -81,47 +99,30 @@ __global__ __launch_bounds__(kBlock) void cg_update1_kernel(int64_t n, int64_t p
                                                             int lpr, int rpp, V* __restrict__ rr_partial) {
     __shared__ V red[kBlock * VEC];
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool act = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     V alpha[VEC], acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         acc[v] = 0;
-        alpha[v] = act ? scal[p + c + v] : (V)0;
+        alpha[v] = L.on ? scal[p + L.c + v] : (V)0;
     }
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V rv[VEC], av[VEC], xv[VEC], pvv[VEC];
+        load_vec<V, VEC>(r + o, rv);
+        load_vec<V, VEC>(Ap + o, av);
+        load_vec<V, VEC>(x + o, xv);
+        load_vec<V, VEC>(pv + o, pvv);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (act && row < n) {
-            const int64_t o = row * p + c;
-            V rv[VEC], av[VEC], xv[VEC], pvv[VEC];
-            load_vec<V, VEC>(r + o, rv);
-            load_vec<V, VEC>(Ap + o, av);
-            load_vec<V, VEC>(x + o, xv);
-            load_vec<V, VEC>(pv + o, pvv);
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                rv[v] = fma(-alpha[v], av[v], rv[v]);   // r -= alpha·Ap   (linear_cg.py:78)
-                xv[v] = fma(alpha[v], pvv[v], xv[v]);   // x += alpha·p    (linear_cg.py:32)
-                acc[v] = fma(rv[v], rv[v], acc[v]);     // rᵀr             (linear_cg.py:36-37)
-            }
-            store_vec<V, VEC>(r + o, rv);
-            store_vec<V, VEC>(x + o, xv);
+        for (int v = 0; v < VEC; ++v) {
+            rv[v] = fma(-alpha[v], av[v], rv[v]);   // r -= alpha·Ap   (linear_cg.py:78)
+            xv[v] = fma(alpha[v], pvv[v], xv[v]);   // x += alpha·p    (linear_cg.py:32)
+            acc[v] = fma(rv[v], rv[v], acc[v]);     // rᵀr             (linear_cg.py:36-37)
         }
-    }
-    if (rs < rpp) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) red[(rs * lpr + cl) * VEC + v] = acc[v];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V s = 0;
-        for (int k = 0; k < rpp; ++k) s += red[k * lpr * VEC + cc];
-        rr_partial[(int64_t)blockIdx.x * p + cc] = s;
-    }
+        store_vec<V, VEC>(r + o, rv);
+        store_vec<V, VEC>(x + o, xv);
+    });
+    fold_partial_row<V, VEC>(red, acc, L, p, rr_partial + (int64_t)blockIdx.x * p);
 }
 
 // Steps 1 + 2 in one launch when K1 left few partial rows (the plane sweep: one per workgroup): EVERY workgroup of the update sums
@@ -143,54 +144,37 @@ __global__ __launch_bounds__(kBlock) void cg_update1_alpha_kernel(int64_t n, int
         const V pap = block_colsum<V>(pap_partial, n_partial, p, c0, w, red);
         if (t < w) {
             const int64_t c = c0 + t;
-            V a = pap < eps ? (V)0 : scal[c] / pap;          // safe division (linear_cg.py:67-71)
-            if (flags[2 + c] != 0) a = 0;                     // converged columns are frozen (:74)
+            const V a = cg_safe_alpha(scal[c], pap, eps, flags[2 + c] != 0);
             alpha_s[c] = a;
             if (blockIdx.x == 0) scal[p + c] = a;             // (kept in the state for diagnostics; nobody reads it in this launch)
         }
         __syncthreads();
     }
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool act = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     V alpha[VEC], acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         acc[v] = 0;
-        alpha[v] = act ? alpha_s[c + v] : (V)0;
+        alpha[v] = L.on ? alpha_s[L.c + v] : (V)0;
     }
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V rv[VEC], av[VEC], xv[VEC], pvv[VEC];
+        load_vec<V, VEC>(r + o, rv);
+        load_vec<V, VEC>(Ap + o, av);
+        load_vec<V, VEC>(x + o, xv);
+        load_vec<V, VEC>(pv + o, pvv);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (act && row < n) {
-            const int64_t o = row * p + c;
-            V rv[VEC], av[VEC], xv[VEC], pvv[VEC];
-            load_vec<V, VEC>(r + o, rv);
-            load_vec<V, VEC>(Ap + o, av);
-            load_vec<V, VEC>(x + o, xv);
-            load_vec<V, VEC>(pv + o, pvv);
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                rv[v] = fma(-alpha[v], av[v], rv[v]);   // r -= alpha·Ap   (linear_cg.py:78)
-                xv[v] = fma(alpha[v], pvv[v], xv[v]);   // x += alpha·p    (linear_cg.py:32)
-                acc[v] = fma(rv[v], rv[v], acc[v]);     // rᵀr             (linear_cg.py:36-37)
-            }
-            store_vec<V, VEC>(r + o, rv);
-            store_vec<V, VEC>(x + o, xv);
+        for (int v = 0; v < VEC; ++v) {
+            rv[v] = fma(-alpha[v], av[v], rv[v]);   // r -= alpha·Ap   (linear_cg.py:78)
+            xv[v] = fma(alpha[v], pvv[v], xv[v]);   // x += alpha·p    (linear_cg.py:32)
+            acc[v] = fma(rv[v], rv[v], acc[v]);     // rᵀr             (linear_cg.py:36-37)
         }
-    }
-    __syncthreads();
-    if (rs < rpp) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) red[(rs * lpr + cl) * VEC + v] = acc[v];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V s = 0;
-        for (int k = 0; k < rpp; ++k) s += red[k * lpr * VEC + cc];
-        rr_partial[(int64_t)blockIdx.x * p + cc] = s;
-    }
+        store_vec<V, VEC>(r + o, rv);
+        store_vec<V, VEC>(x + o, xv);
+    });
+    __syncthreads();                        // `red` served block_colsum above
+    fold_partial_row<V, VEC>(red, acc, L, p, rr_partial + (int64_t)blockIdx.x * p);
 }
 
 template <typename V>
@@ -211,31 +195,22 @@ __global__ __launch_bounds__(kBlock) void cg_beta_kernel(const V* __restrict__ r
         const V ip_new = rz_partial ? block_colsum<V>(rz_partial, n_rz, p, c0, w, red) : rr_new;
         if (t < w) {
             const int64_t c = c0 + t;
-            const V rr_old = scal[c];
-            // beta = <r,z>_new / <r,z>_old with the reference's safe division (linear_cg.py:35-43)
-            const V beta = rr_old < eps ? (V)0 : ip_new / rr_old;
+            const CgColumn<V> col = cg_beta_norm(ip_new, scal[c], rr_new, eps, flags[2 + p + c] != 0, stop_after);
             scal[c] = ip_new;
-            scal[2 * p + c] = beta;
-            V nrm = sqrt(rr_new);                       // ‖r‖₂ (linear_cg.py:372)
-            if (flags[2 + p + c] != 0) nrm = 0;         // rhs_is_zero mask (:373)
-            scal[3 * p + c] = nrm;
-            flags[2 + c] = nrm < stop_after ? 1 : 0;    // has_converged (:374)
-            my_norm_sum += nrm;
+            scal[2 * p + c] = col.beta;
+            scal[3 * p + c] = col.norm;
+            flags[2 + c] = col.has_converged;
+            my_norm_sum += col.norm;
         }
     }
     normsum[t] = t < 64 ? my_norm_sum : (V)0;
     __syncthreads();
     if (t == 0) {
-        V s = 0;
-        const int lim = p < 64 ? (int)p : 64;
-        for (int k = 0; k < lim; ++k) s += normsum[k];
-        const V mean = s / (V)p;
         // iter_index < 0: the iteration counter lives on the device (flags[1]), so that every iteration is the
         // same launch and a chunk of iterations can be replayed as one hipGraph.
         const int it = iter_index < 0 ? flags[1] : iter_index;
         flags[1] = it + 1;
-        // stop rule (linear_cg.py:376-382): k >= min(10, max_iter-1) and mean‖r‖ < tol
-        if (it >= min_iter_index && mean < tolerance) flags[0] = 1;
+        if (cg_mean_norm_stops(normsum, p, it, min_iter_index, tolerance)) flags[0] = 1;
     }
 }
 
@@ -244,27 +219,20 @@ __global__ __launch_bounds__(kBlock) void cg_update2_kernel(int64_t n, int64_t p
                                                             const V* __restrict__ scal, const int* __restrict__ flags,
                                                             int lpr, int rpp) {
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    if (!(rs < rpp && c < p)) return;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
+    if (!L.on) return;
     V beta[VEC];
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) beta[v] = scal[2 * p + c + v];
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for (int v = 0; v < VEC; ++v) beta[v] = scal[2 * p + L.c + v];
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V rv[VEC], pvv[VEC];
+        load_vec<V, VEC>(r + o, rv);
+        load_vec<V, VEC>(pv + o, pvv);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (row < n) {
-            const int64_t o = row * p + c;
-            V rv[VEC], pvv[VEC];
-            load_vec<V, VEC>(r + o, rv);
-            load_vec<V, VEC>(pv + o, pvv);
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) pvv[v] = fma(pvv[v], beta[v], rv[v]);  // p = r + beta·p (linear_cg.py:47)
-            store_vec<V, VEC>(pv + o, pvv);
-        }
-    }
+        for (int v = 0; v < VEC; ++v) pvv[v] = fma(pvv[v], beta[v], rv[v]);  // p = r + beta·p (linear_cg.py:47)
+        store_vec<V, VEC>(pv + o, pvv);
+    });
 }
 
 // ---- CG, two launches after K1 (state in two halves that alternate by iteration) ---------------------------------------------
@@ -285,30 +253,22 @@ __global__ __launch_bounds__(kBlock) void cg_residual_alpha_kernel(int64_t n, in
     __shared__ V alpha_s[kBlock];        // p <= kBlock columns (checked by the launcher)
     if (flags[par] != 0) return;
     const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool act = rs < rpp && c < p;
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses * groups;
+    const Lanes L = lanes<VEC>(p, lpr, rpp, groups);
     constexpr int NP = GROUPS > 0 ? GROUPS * kPasses : 1;
     V rv[NP][VEC], av[NP][VEC];
     if constexpr (GROUPS > 0) {
         // the streaming loads go out first: the sum of the partial rows below (two dependent trips to L2) then overlaps them
-#pragma unroll
-        for (int ps = 0; ps < NP; ++ps) {
-            const int64_t row = r0 + (int64_t)ps * rpp + rs;
-            if (act && row < n) {
-                load_vec<V, VEC>(r + row * p + c, rv[ps]);
-                load_vec<V, VEC>(Ap + row * p + c, av[ps]);
-            }
-        }
+        for_rows<NP>(L, n, [&](int ps, int64_t row) {
+            load_vec<V, VEC>(r + row * p + L.c, rv[ps]);
+            load_vec<V, VEC>(Ap + row * p + L.c, av[ps]);
+        });
     }
     for (int64_t c0 = 0; c0 < p; c0 += 64) {
         const int w = (int)(p - c0 < 64 ? p - c0 : 64);
         const V pap = block_colsum<V>(pap_partial, n_partial, p, c0, w, red);
         if (t < w) {
             const int64_t cc = c0 + t;
-            V a = pap < eps ? (V)0 : scal[(int64_t)par * p + cc] / pap;         // safe division (linear_cg.py:67-71)
-            if (flags[4 + (int64_t)par * p + cc] != 0) a = 0;                   // converged columns are frozen (:74)
+            const V a = cg_safe_alpha(scal[(int64_t)par * p + cc], pap, eps, flags[4 + (int64_t)par * p + cc] != 0);
             alpha_s[cc] = a;
             if (blockIdx.x == 0) scal[2 * p + cc] = a;                          // for the direction update (the next launch)
         }
@@ -318,51 +278,34 @@ __global__ __launch_bounds__(kBlock) void cg_residual_alpha_kernel(int64_t n, in
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         acc[v] = 0;
-        alpha[v] = act ? alpha_s[c + v] : (V)0;
+        alpha[v] = L.on ? alpha_s[L.c + v] : (V)0;
     }
     if constexpr (GROUPS > 0) {
+        for_rows<NP>(L, n, [&](int ps, int64_t row) {
 #pragma unroll
-        for (int ps = 0; ps < NP; ++ps) {
-            const int64_t row = r0 + (int64_t)ps * rpp + rs;
-            if (act && row < n) {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    rv[ps][v] = fma(-alpha[v], av[ps][v], rv[ps][v]);   // r -= alpha·Ap   (linear_cg.py:78)
-                    acc[v] = fma(rv[ps][v], rv[ps][v], acc[v]);         // rᵀr             (linear_cg.py:36-37)
-                }
-                store_vec<V, VEC>(r + row * p + c, rv[ps]);
+            for (int v = 0; v < VEC; ++v) {
+                rv[ps][v] = fma(-alpha[v], av[ps][v], rv[ps][v]);   // r -= alpha·Ap   (linear_cg.py:78)
+                acc[v] = fma(rv[ps][v], rv[ps][v], acc[v]);         // rᵀr             (linear_cg.py:36-37)
             }
-        }
+            store_vec<V, VEC>(r + row * p + L.c, rv[ps]);
+        });
     } else {
         for (int g = 0; g < groups; ++g) {
+            for_rows(L, n, [&](int, int64_t row) {
+                const int64_t o = row * p + L.c;
+                load_vec<V, VEC>(r + o, rv[0]);
+                load_vec<V, VEC>(Ap + o, av[0]);
 #pragma unroll
-            for (int ps = 0; ps < kPasses; ++ps) {
-                const int64_t row = r0 + ((int64_t)g * kPasses + ps) * rpp + rs;
-                if (act && row < n) {
-                    const int64_t o = row * p + c;
-                    load_vec<V, VEC>(r + o, rv[0]);
-                    load_vec<V, VEC>(Ap + o, av[0]);
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) {
-                        rv[0][v] = fma(-alpha[v], av[0][v], rv[0][v]);
-                        acc[v] = fma(rv[0][v], rv[0][v], acc[v]);
-                    }
-                    store_vec<V, VEC>(r + o, rv[0]);
+                for (int v = 0; v < VEC; ++v) {
+                    rv[0][v] = fma(-alpha[v], av[0][v], rv[0][v]);
+                    acc[v] = fma(rv[0][v], rv[0][v], acc[v]);
                 }
-            }
+                store_vec<V, VEC>(r + o, rv[0]);
+            }, g * kPasses);
         }
     }
-    __syncthreads();
-    if (rs < rpp) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) red[(rs * lpr + cl) * VEC + v] = acc[v];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V s = 0;
-        for (int k = 0; k < rpp; ++k) s += red[k * lpr * VEC + cc];
-        rr_partial[(int64_t)blockIdx.x * p + cc] = s;
-    }
+    __syncthreads();                        // `red` served block_colsum above
+    fold_partial_row<V, VEC>(red, acc, L, p, rr_partial + (int64_t)blockIdx.x * p);
 }
 
 template <typename V, int VEC>
@@ -380,46 +323,38 @@ __global__ __launch_bounds__(kBlock) void cg_direction_beta_kernel(int64_t n, in
         return;
     }
     const bool first = blockIdx.x == 0;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool act = rs < rpp && c < p;
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     // the streaming loads go out first: the sum of the partial rows (dependent trips to L2) overlaps them
     V rv[kPasses][VEC], pvv[kPasses][VEC], xv[kPasses][VEC];
-#pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (act && row < n) {
-            const int64_t o = row * p + c;
-            load_vec<V, VEC>(r + o, rv[ps]);
-            load_vec<V, VEC>(pv + o, pvv[ps]);
-            load_vec<V, VEC>(x + o, xv[ps]);
-        }
-    }
+    for_rows(L, n, [&](int ps, int64_t row) {
+        const int64_t o = row * p + L.c;
+        load_vec<V, VEC>(r + o, rv[ps]);
+        load_vec<V, VEC>(pv + o, pvv[ps]);
+        load_vec<V, VEC>(x + o, xv[ps]);
+    });
     V my_norm_sum = 0;
     for (int64_t c0 = 0; c0 < p; c0 += 64) {
         const int w = (int)(p - c0 < 64 ? p - c0 : 64);
         const V rr_new = block_colsum<V>(rr_partial, n_partial, p, c0, w, red);
         if (t < w) {
             const int64_t c = c0 + t;
-            const V rr_old = scal[(int64_t)par * p + c];
-            const V beta = rr_old < eps ? (V)0 : rr_new / rr_old;     // safe division (linear_cg.py:35-43)
+            // (every workgroup needs beta; only the first one keeps the norm, so only it reads the rhs_is_zero mask)
+            const CgColumn<V> col = cg_beta_norm(rr_new, scal[(int64_t)par * p + c], rr_new, eps, first && flags[4 + 2 * p + c] != 0,
+                                                 stop_after);
             alpha_s[c] = scal[2 * p + c];
-            beta_s[c] = beta;
+            beta_s[c] = col.beta;
             if (first) {
                 // the coefficients of the first n_hist iterations, for the Lanczos tridiagonal matrices (linear_cg.py:385-406):
                 // hist[it][0][c] = alpha, hist[it][1][c] = beta
                 if (hist != nullptr && flags[2] < n_hist) {
                     hist[((int64_t)flags[2] * 2 + 0) * p + c] = scal[2 * p + c];
-                    hist[((int64_t)flags[2] * 2 + 1) * p + c] = beta;
+                    hist[((int64_t)flags[2] * 2 + 1) * p + c] = col.beta;
                 }
                 scal[(int64_t)(par ^ 1) * p + c] = rr_new;
-                scal[3 * p + c] = beta;
-                V nrm = sqrt(rr_new);                                  // |r|_2 (linear_cg.py:372)
-                if (flags[4 + 2 * p + c] != 0) nrm = 0;                // rhs_is_zero mask (:373)
-                scal[4 * p + c] = nrm;
-                flags[4 + (int64_t)(par ^ 1) * p + c] = nrm < stop_after ? 1 : 0;     // has_converged (:374)
-                my_norm_sum += nrm;
+                scal[3 * p + c] = col.beta;
+                scal[4 * p + c] = col.norm;
+                flags[4 + (int64_t)(par ^ 1) * p + c] = col.has_converged;
+                my_norm_sum += col.norm;
             }
         }
     }
@@ -427,38 +362,29 @@ __global__ __launch_bounds__(kBlock) void cg_direction_beta_kernel(int64_t n, in
         if (t < 64) normsum[t] = my_norm_sum;
         __syncthreads();
         if (t == 0) {
-            V s = 0;
-            const int lim = p < 64 ? (int)p : 64;
-            for (int k = 0; k < lim; ++k) s += normsum[k];
-            const V mean = s / (V)p;
             const int it = flags[2];
             flags[2] = it + 1;
-            // stop rule (linear_cg.py:376-382): k >= min(10, max_iter-1) and mean|r| < tol
-            flags[par ^ 1] = (it >= min_iter_index && mean < tolerance) ? 1 : 0;
+            flags[par ^ 1] = cg_mean_norm_stops(normsum, p, it, min_iter_index, tolerance) ? 1 : 0;
         }
     }
     __syncthreads();
-    if (!act) return;
+    if (!L.on) return;
     V alpha[VEC], beta[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-        alpha[v] = alpha_s[c + v];
-        beta[v] = beta_s[c + v];
+        alpha[v] = alpha_s[L.c + v];
+        beta[v] = beta_s[L.c + v];
     }
+    for_rows(L, n, [&](int ps, int64_t row) {
+        const int64_t o = row * p + L.c;
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (row < n) {
-            const int64_t o = row * p + c;
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                xv[ps][v] = fma(alpha[v], pvv[ps][v], xv[ps][v]);      // x += alpha·p    (linear_cg.py:32) — with the direction alpha belongs to
-                pvv[ps][v] = fma(pvv[ps][v], beta[v], rv[ps][v]);      // p = r + beta·p  (linear_cg.py:47)
-            }
-            store_vec<V, VEC>(x + o, xv[ps]);
-            store_vec<V, VEC>(pv + o, pvv[ps]);
+        for (int v = 0; v < VEC; ++v) {
+            xv[ps][v] = fma(alpha[v], pvv[ps][v], xv[ps][v]);      // x += alpha·p    (linear_cg.py:32) — with the direction alpha belongs to
+            pvv[ps][v] = fma(pvv[ps][v], beta[v], rv[ps][v]);      // p = r + beta·p  (linear_cg.py:47)
         }
-    }
+        store_vec<V, VEC>(x + o, xv[ps]);
+        store_vec<V, VEC>(pv + o, pvv[ps]);
+    });
 }
 
 }  // namespace tsgu

@@ -3,10 +3,16 @@
 // every entry point of the three files is written on.  From tsgu_common.h, shared with every other kernel family:
 //   with_value_type(vtype, f)        calls the generic lambda f with a float or a double tag (`using V = decltype(tag)`)
 //   launch(kern, blocks, s, args...) one kernel on `blocks` workgroups of kBlock threads, then check_launch()
-// and here:
+// and here, host side:
 //   launch_lanes<V>(n, p, scalar, wide, go)   geometry of an [n][p] array, then go(instance, geometry) with the scalar-lane or
 //                                    the wide-lane instance of a kernel — its argument list is written once, in `go`
 //   fold_partials<V>(...)            the fold-then-finalise prefix of the single-workgroup scalar kernels
+// device side (what the streaming kernels of the three files are written on):
+//   lanes<VEC>(p, lpr, rpp)          a thread's place in the lane layout: its columns, its row slot, the workgroup's first row
+//   for_rows<NP>(L, n, f)            f(pass, row) for the rows the thread owns, NP passes unrolled (bicg_update_x_kernel keeps a
+//                                    loop of its own, see there)
+//   fold_partial_row<V, VEC>(...)    the workgroup's partial row: every lane's accumulators summed per column in a fixed order
+//   block_colsum<Acc>(...)           the sum of partial rows over a 64-column window, by one workgroup, in a fixed order
 #pragma once
 
 #include "tsgu_common.h"
@@ -32,6 +38,61 @@ inline bool vec_geom(int wide, bool can_wide, int64_t n, int64_t p, VecGeom& g) 
     const int64_t rows_per_block = (int64_t)g.rpp * kPasses;
     g.blocks = (n + rows_per_block - 1) / rows_per_block;
     return true;
+}
+
+// A thread's place in that layout: thread t is lane cl of row slot rs, holds columns [c, c + VEC) and, in pass ps, row
+// r0 + ps * rpp + rs of the workgroup's rpp * kPasses (* groups) rows.  `on`: the thread has a row slot and columns (lpr need not
+// divide kBlock, and the slots past rpp are idle).
+struct Lanes {
+    int lpr, rpp;
+    int cl, rs;
+    int64_t c;
+    bool on;
+    int64_t r0;
+};
+
+template <int VEC>
+__device__ __forceinline__ Lanes lanes(int64_t p, int lpr, int rpp, int groups = 1) {
+    const int t = threadIdx.x;
+    Lanes L;
+    L.lpr = lpr;
+    L.rpp = rpp;
+    L.cl = t % lpr;
+    L.rs = t / lpr;
+    L.c = (int64_t)L.cl * VEC;
+    L.on = L.rs < rpp && L.c < p;
+    L.r0 = (int64_t)blockIdx.x * rpp * kPasses * groups;
+    return L;
+}
+
+// f(ps, row) for the rows below n that the thread owns in passes ps0 ... ps0 + NP - 1 (f sees ps = 0 ... NP - 1: the index of
+// what a kernel keeps in registers between two walks).  Fully unrolled.  f must not hold a barrier: lanes skip rows.
+template <int NP = kPasses, typename F>
+__device__ __forceinline__ void for_rows(const Lanes& L, int64_t n, F&& f, int ps0 = 0) {
+#pragma unroll
+    for (int ps = 0; ps < NP; ++ps) {
+        const int64_t row = L.r0 + (int64_t)(ps0 + ps) * L.rpp + L.rs;
+        if (L.on && row < n) f(ps, row);
+    }
+}
+
+// The workgroup's partial row: dst[cc] = the sum over the row slots k = 0 ... rpp - 1, in that order, of the accumulator lane
+// (k, cc) holds for column cc.  No atomics and a fixed order: what makes every reduction of these solvers deterministic.
+// red: LDS scratch of kBlock * VEC values; one barrier between the writes and the sums, none after the sums (a caller that
+// writes `red` again puts one there); called by every thread of the workgroup.
+template <typename V, int VEC>
+__device__ __forceinline__ void fold_partial_row(V* red, const V (&acc)[VEC], const Lanes& L, int64_t p, V* __restrict__ dst) {
+    const int lpr = L.lpr, rpp = L.rpp, cl = L.cl, rs = L.rs;
+    if (rs < rpp) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) red[(rs * lpr + cl) * VEC + v] = acc[v];
+    }
+    __syncthreads();
+    for (int64_t cc = threadIdx.x; cc < p; cc += kBlock) {
+        V s = 0;
+        for (int k = 0; k < rpp; ++k) s += red[k * lpr * VEC + cc];
+        dst[cc] = s;
+    }
 }
 
 // Sum partial[b][c] over b for the calling block's column window [c0, c0+w): result valid

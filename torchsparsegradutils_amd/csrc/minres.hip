@@ -111,45 +111,28 @@ __global__ __launch_bounds__(kBlock) void minres_lanczos_kernel(int64_t n, int64
                                                                 V* __restrict__ partial, V value) {
     __shared__ V red[kBlock * VEC];
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool on = rs < rpp && c < p;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     V alpha[VEC], beta[VEC], acc[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
         acc[k] = 0;
-        alpha[k] = on ? scal[c + k] : (V)0;
-        beta[k] = on ? scal[11 * p + c + k] : (V)0;
+        alpha[k] = L.on ? scal[L.c + k] : (V)0;
+        beta[k] = L.on ? scal[11 * p + L.c + k] : (V)0;
     }
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    for_rows(L, n, [&](int, int64_t row) {
+        const int64_t o = row * p + L.c;
+        V a[VEC], b[VEC], pr[VEC];
+        load_vec<V, VEC>(zpp + o, a);
+        load_vec<V, VEC>(zp + o, b);
+        load_vec<V, VEC>(prod + o, pr);
 #pragma unroll
-    for (int ps = 0; ps < kPasses; ++ps) {
-        const int64_t row = r0 + (int64_t)ps * rpp + rs;
-        if (on && row < n) {
-            const int64_t o = row * p + c;
-            V a[VEC], b[VEC], pr[VEC];
-            load_vec<V, VEC>(zpp + o, a);
-            load_vec<V, VEC>(zp + o, b);
-            load_vec<V, VEC>(prod + o, pr);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                a[k] = (mul_rn(value, pr[k]) - alpha[k] * b[k]) - beta[k] * a[k];  // value*A q rounded as the reference's .mul(value)
-                acc[k] = fma(a[k], a[k], acc[k]);
-            }
-            store_vec<V, VEC>(zpp + o, a);
+        for (int k = 0; k < VEC; ++k) {
+            a[k] = (mul_rn(value, pr[k]) - alpha[k] * b[k]) - beta[k] * a[k];  // value*A q rounded as the reference's .mul(value)
+            acc[k] = fma(a[k], a[k], acc[k]);
         }
-    }
-    if (rs < rpp) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) red[(rs * lpr + cl) * VEC + k] = acc[k];
-    }
-    __syncthreads();
-    for (int64_t cc = t; cc < p; cc += kBlock) {
-        V sum = 0;
-        for (int k = 0; k < rpp; ++k) sum += red[k * lpr * VEC + cc];
-        partial[(int64_t)blockIdx.x * p + cc] = sum;
-    }
+        store_vec<V, VEC>(zpp + o, a);
+    });
+    fold_partial_row<V, VEC>(red, acc, L, p, partial + (int64_t)blockIdx.x * p);
 }
 
 // z_c /= beta_c (in place; also q_c when a preconditioner produced one);  per shift: w_c = ((q_p - sub w_p) - subsub w_pp) / diag
@@ -163,11 +146,7 @@ __global__ __launch_bounds__(kBlock) void minres_update_kernel(int64_t n, int64_
                                                                V* __restrict__ qc, int n_shift, int64_t np) {
     __shared__ V red[kBlock * VEC];
     if (flags[0] != 0) return;
-    const int t = threadIdx.x;
-    const int cl = t % lpr, rs = t / lpr;
-    const int64_t c = (int64_t)cl * VEC;
-    const bool on = rs < rpp && c < p;
-    const int64_t r0 = (int64_t)blockIdx.x * rpp * kPasses;
+    const Lanes L = lanes<VEC>(p, lpr, rpp);
     for (int sh = 0; sh < n_shift; ++sh) {
         const V* blk = scal + (int64_t)sh * 12 * p;
         V* wpp_s = wpp + sh * np;
@@ -177,60 +156,50 @@ __global__ __launch_bounds__(kBlock) void minres_update_kernel(int64_t n, int64_
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             au[k] = as[k] = 0;
-            beta[k] = on ? scal[p + c + k] : (V)1;
-            sub[k] = on ? blk[7 * p + c + k] : (V)0;
-            subsub[k] = on ? blk[8 * p + c + k] : (V)0;
-            diag[k] = on ? blk[9 * p + c + k] : (V)1;
-            scale[k] = on ? blk[10 * p + c + k] : (V)0;
+            beta[k] = L.on ? scal[p + L.c + k] : (V)1;
+            sub[k] = L.on ? blk[7 * p + L.c + k] : (V)0;
+            subsub[k] = L.on ? blk[8 * p + L.c + k] : (V)0;
+            diag[k] = L.on ? blk[9 * p + L.c + k] : (V)1;
+            scale[k] = L.on ? blk[10 * p + L.c + k] : (V)0;
         }
+        for_rows(L, n, [&](int, int64_t row) {
+            const int64_t o = row * p + L.c;
+            V q[VEC], w2[VEC], w1[VEC], x[VEC];
+            if (sh == 0) {
+                V z[VEC];
+                load_vec<V, VEC>(zc + o, z);
 #pragma unroll
-        for (int ps = 0; ps < kPasses; ++ps) {
-            const int64_t row = r0 + (int64_t)ps * rpp + rs;
-            if (on && row < n) {
-                const int64_t o = row * p + c;
-                V q[VEC], w2[VEC], w1[VEC], x[VEC];
-                if (sh == 0) {
-                    V z[VEC];
-                    load_vec<V, VEC>(zc + o, z);
+                for (int k = 0; k < VEC; ++k) z[k] = z[k] / beta[k];
+                store_vec<V, VEC>(zc + o, z);
+                if (qc) {
+                    load_vec<V, VEC>(qc + o, z);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) z[k] = z[k] / beta[k];
-                    store_vec<V, VEC>(zc + o, z);
-                    if (qc) {
-                        load_vec<V, VEC>(qc + o, z);
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) z[k] = z[k] / beta[k];
-                        store_vec<V, VEC>(qc + o, z);
-                    }
+                    store_vec<V, VEC>(qc + o, z);
                 }
-                load_vec<V, VEC>(qp + o, q);
-                load_vec<V, VEC>(wpp_s + o, w2);
-                load_vec<V, VEC>(wp_s + o, w1);
-                load_vec<V, VEC>(sol_s + o, x);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    const V wc = ((q[k] - sub[k] * w1[k]) - subsub[k] * w2[k]) / diag[k];
-                    const V up = wc * scale[k];
-                    w2[k] = wc;
-                    x[k] = x[k] + up;
-                    au[k] = fma(up, up, au[k]);
-                    as[k] = fma(x[k], x[k], as[k]);
-                }
-                store_vec<V, VEC>(wpp_s + o, w2);
-                store_vec<V, VEC>(sol_s + o, x);
             }
-        }
+            load_vec<V, VEC>(qp + o, q);
+            load_vec<V, VEC>(wpp_s + o, w2);
+            load_vec<V, VEC>(wp_s + o, w1);
+            load_vec<V, VEC>(sol_s + o, x);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const V wc = ((q[k] - sub[k] * w1[k]) - subsub[k] * w2[k]) / diag[k];
+                const V up = wc * scale[k];
+                w2[k] = wc;
+                x[k] = x[k] + up;
+                au[k] = fma(up, up, au[k]);
+                as[k] = fma(x[k], x[k], as[k]);
+            }
+            store_vec<V, VEC>(wpp_s + o, w2);
+            store_vec<V, VEC>(sol_s + o, x);
+        });
         if (!with_norms) continue;
         for (int set = 0; set < 2; ++set) {
-            if (rs < rpp) {
+            V a[VEC];
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) red[(rs * lpr + cl) * VEC + k] = set == 0 ? au[k] : as[k];
-            }
-            __syncthreads();
-            for (int64_t cc = t; cc < p; cc += kBlock) {
-                V sum = 0;
-                for (int k = 0; k < rpp; ++k) sum += red[k * lpr * VEC + cc];
-                partial[(2 * sh + set) * set_stride + (int64_t)blockIdx.x * p + cc] = sum;
-            }
+            for (int k = 0; k < VEC; ++k) a[k] = set == 0 ? au[k] : as[k];
+            fold_partial_row<V, VEC>(red, a, L, p, partial + (2 * sh + set) * set_stride + (int64_t)blockIdx.x * p);
             __syncthreads();
         }
     }
