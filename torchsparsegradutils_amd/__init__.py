@@ -3,7 +3,7 @@
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
-``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_lobpcg`` beside them;
+``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_lobpcg`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -11,6 +11,7 @@ from ._backend import poll_errors
 from ._compat import linalg_solve_triangular_compat
 from ._pattern import wait_for_plans
 from .indexed_matmul import GatherMM, SegmentMM, gather_mm, segment_mm
+from .sparse_amg import SparseAMG, sparse_amg
 from .sparse_attention import SparseAttention, sparse_attention
 from .sparse_bsr_attention import SparseBSRAttention, sparse_bsr_attention
 from .sparse_bsr_mm import SparseBSRMatMul, sparse_bsr_mm
@@ -42,6 +43,8 @@ __all__ = [
     "SparseIC0",
     "sparse_fsai",
     "SparseFSAI",
+    "sparse_amg",
+    "SparseAMG",
     "sparse_lobpcg",
     "SparseLOBPCG",
     "gather_mm",

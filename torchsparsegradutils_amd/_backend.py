@@ -269,6 +269,19 @@ SIGNATURES_LOBPCG = {
 # header of csrc/ -> its table: bound by `load_library` after `ABI` (tests/test_sparse_lobpcg_cpu.py holds it against the header)
 STAGED = {"tsgu_hip_lobpcg.h": SIGNATURES_LOBPCG}
 
+# the additive entries of csrc/tsgu_hip_amg.h (same library, same ABI version): the second STAGED header.  It has a registry of its
+# own because tests pin `ABI` against include/ and `STAGED` to the LOBPCG table ("Adding a header")
+SIGNATURES_AMG = {
+    "tsgu_amg_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_amg_hop": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_amg_mis2_update": (_int, [_int, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_csr_affine_spmm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _dbl,
+                                    _ptr, _i64, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after `ABI` and `STAGED` (tests/test_sparse_amg_cpu.py holds it against the header)
+STAGED_AMG = {"tsgu_hip_amg.h": SIGNATURES_AMG}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -291,7 +304,7 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for table in (*ABI.values(), *STAGED.values()):
+        for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1520,6 +1533,85 @@ def lobpcg_residual(AX, X, lam, out=None, workspace=None, workgroups: int = 0):
     launch("tsgu_lobpcg_residual", dev, vtype_of(ref), ref.size(0), k, AX, _ld(AX), X, _ld(X), lam, out, _ld(out), sumsq, workspace,
            workspace.numel() * workspace.element_size(), int(workgroups))
     return out, sumsq
+
+
+def amg_geometry():
+    """(group widths the hop accepts — the powers of two between the library's limits —, column tile of the affine product)
+    (csrc/tsgu_hip_amg.h).  Host only."""
+    lo, hi, tile = _query("tsgu_amg_geometry")
+    widths = []
+    while lo <= hi:
+        widths.append(lo)
+        lo *= 2
+    return tuple(widths), tile
+
+
+def _amg_keys(what: str, n: int, *keys):
+    for k in keys:
+        if k is not None and (k.dtype != torch.int64 or k.shape != (n,) or not k.is_contiguous()):
+            raise RuntimeError(f"{what}: keys are contiguous int64 vectors of {n} words (the bits of unsigned 64-bit keys)")
+
+
+def amg_hop(ptr, idx, keys, n: int, group: int = 8, out=None):
+    """out[i] = max(keys[i], max of keys[j] over the stored entries (i, j)) in UNSIGNED 64-bit order, on the CSR pattern (ptr, idx).
+    Keys travel as int64 tensors holding the bits.  `group`: lanes per row, one of `amg_geometry()[0]` (speed only: the result
+    does not depend on it).  `out` may not overlap `keys`."""
+    dev = require_device(ptr, idx, keys, out)
+    if ptr.numel() != n + 1 or ptr.dtype != idx.dtype:
+        raise RuntimeError(f"tsgu_csr_amg_hop: {n} rows need a row pointer of {n + 1} words of the columns' dtype, got {ptr.numel()} "
+                           f"({ptr.dtype} / {idx.dtype})")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+    _amg_keys("tsgu_csr_amg_hop", n, keys, out)
+    ptr, idx = ptr.contiguous(), idx.contiguous()
+    launch("tsgu_csr_amg_hop", dev, itype_of(ptr), n, idx.numel(), ptr, idx if idx.numel() else None, keys, out, int(group))
+    return out
+
+
+AMG_INIT, AMG_ROUND, AMG_ROOTS = 0, 1, 2
+
+
+def amg_mis2_update(mode: int, n: int, key=None, t=None, out=None, undecided=None, device=None):
+    """One node-wise step of the MIS-2 aggregation (csrc/tsgu_hip_amg.h): AMG_INIT writes the initial keys, AMG_ROUND applies the
+    state machine to (key, t = hop(hop(key))) and sets the device word `undecided` (zeroed by the caller) when a node stays
+    undecided, AMG_ROOTS keeps the roots' keys and zeroes the rest.  Returns `out` (AMG_ROUND may write `key` in place)."""
+    dev = require_device(key, t, out, undecided) or device
+    if dev is None:
+        raise RuntimeError("tsgu_amg_mis2_update: a device is required when no tensor names one")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+    _amg_keys("tsgu_amg_mis2_update", n, key, t, out)
+    if undecided is not None and (undecided.dtype != torch.int64 or undecided.numel() != 1):
+        raise RuntimeError("tsgu_amg_mis2_update: `undecided` is one int64 word")
+    launch("tsgu_amg_mis2_update", dev, int(mode), n, key, t, out, undecided)
+    return out
+
+
+def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, w=None, alpha: float = 1.0, out=None):
+    """out = C + alpha·w∘(B − A·X) for the CSR matrix (ptr, idx, val) of shape (n_rows, n_cols) and row-major X (n_cols, p); C, B
+    (n_rows, p) and w (n_rows,) are optional (None: 0, 0 and 1).  One launch (csrc/tsgu_hip_amg.h).  `out` may be C or B; it may
+    not overlap X (the library refuses it).  float32 and float64."""
+    if val.dtype not in FACTOR_DTYPES:
+        raise TypeError(f"tsgu_csr_affine_spmm: float32 and float64 values only, got {val.dtype}")
+    dev = require_device(ptr, idx, val, X, C, B, w, out)
+    p = X.size(1) if X.dim() == 2 else -1
+    dense = [t for t in (X, C, B, out) if t is not None]
+    if (ptr.numel() != n_rows + 1 or ptr.dtype != idx.dtype or idx.numel() != val.numel() or X.dim() != 2 or X.size(0) != n_cols
+            or any(t.dtype != val.dtype for t in dense) or (w is not None and (w.dtype != val.dtype or w.shape != (n_rows,)))
+            or any(t.dim() != 2 or t.shape != (n_rows, p) for t in (C, B, out) if t is not None)
+            or any((t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)) for t in dense)):
+        raise RuntimeError(f"tsgu_csr_affine_spmm: a ({n_rows}, {n_cols}) matrix needs a row pointer of {n_rows + 1} words of the "
+                           f"columns' dtype, as many values as columns, a row-major X ({n_cols}, p) and row-major C, B, out "
+                           f"({n_rows}, p) of the values' dtype, and w ({n_rows},)")
+    if out is None:
+        out = torch.empty((n_rows, p), dtype=val.dtype, device=dev)
+    ptr, idx, val = ptr.contiguous(), idx.contiguous(), val.contiguous()
+    w = None if w is None else w.contiguous()
+    nnz = idx.numel()
+    launch("tsgu_csr_affine_spmm", dev, vtype_of(val), itype_of(ptr), n_rows, n_cols, nnz, p, ptr, idx if nnz else None,
+           val if nnz else None, X if X.numel() else None, _ld(X), C, 0 if C is None else _ld(C), B, 0 if B is None else _ld(B), w,
+           float(alpha), out if out.numel() else None, _ld(out))
+    return out
 
 
 _PENDING = []            # (event or None, pinned / host int32 slot, what, tsgu status)

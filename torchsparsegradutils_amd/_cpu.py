@@ -626,3 +626,66 @@ def lobpcg_residual(AX: torch.Tensor, X: torch.Tensor, lam: torch.Tensor, out=No
     if out is not None:
         R = out.copy_(R)
     return R, (R * R).sum(dim=0)
+
+
+# ---- the primitives of the aggregation multigrid (sparse_amg.py): csrc/tsgu_hip_amg.h in torch ops --------------------------------
+
+_SIGN = -(1 << 63)       # x ^ _SIGN maps the unsigned order of 64-bit words onto the signed order of int64
+
+
+def _rows_of(ptr: torch.Tensor, nnz: int) -> torch.Tensor:
+    n = ptr.numel() - 1
+    return torch.repeat_interleave(torch.arange(n, dtype=torch.int64), (ptr[1:] - ptr[:-1]).to(torch.int64), output_size=nnz)
+
+
+def amg_hop(ptr: torch.Tensor, idx: torch.Tensor, keys: torch.Tensor, n: int, group: int = 8, out=None) -> torch.Tensor:
+    """out[i] = max(keys[i], max of keys[j] over the stored entries (i, j)) in unsigned 64-bit order (the bits travel as int64)."""
+    _cpu_only(ptr, idx, keys, out)
+    s = keys ^ _SIGN
+    far = s.scatter_reduce(0, _rows_of(ptr, idx.numel()), s.index_select(0, idx.to(torch.int64)), "amax", include_self=True) ^ _SIGN
+    return far if out is None else out.copy_(far)
+
+
+def _lowbias32(x: torch.Tensor) -> torch.Tensor:
+    """lowbias32 of the low words of an int64 tensor, in 32-bit arithmetic."""
+    m = 0xFFFFFFFF
+    x = x & m
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & m
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & m
+    return x ^ (x >> 16)
+
+
+def amg_mis2_update(mode: int, n: int, key=None, t=None, out=None, undecided=None, device=None) -> torch.Tensor:
+    """One node-wise step of the MIS-2 aggregation, as `_backend.amg_mis2_update` (mode 0: initial keys, 1: a round, 2: root keys)."""
+    _cpu_only(key, t, out, undecided)
+    low = (1 << 62) - 1
+    if mode == 0:
+        i = torch.arange(n, dtype=torch.int64)
+        nxt = (1 << 62) | ((_lowbias32(i) >> 2) << 32) | i
+    elif mode == 2:
+        nxt = torch.where((key >> 62) == -2, key, torch.zeros_like(key))
+    else:
+        und = (key >> 62) == 1
+        root = und & ((t & 0xFFFFFFFF) == torch.arange(n, dtype=torch.int64))
+        gone = und & ~root & ((t >> 62) == -2)
+        nxt = torch.where(root, (key & low) | _SIGN, torch.where(gone, key & low, key))
+        if undecided is not None:
+            undecided.fill_(int(bool((und & ~root & ~gone).any())))
+    return nxt if out is None else out.copy_(nxt)
+
+
+def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, w=None, alpha: float = 1.0, out=None) -> torch.Tensor:
+    """out = C + alpha·w∘(B − A·X) for the CSR matrix (ptr, idx, val) and X (n_cols, p); None stands for 0, 0 and 1.  A row is summed
+    in entry order (``index_add_``), the epilogue in the kernel's order of operations."""
+    _cpu_only(ptr, idx, val, X, C, B, w, out)
+    ax = torch.zeros((n_rows, X.size(1)), dtype=val.dtype)
+    ax.index_add_(0, _rows_of(ptr, idx.numel()), val.unsqueeze(1) * X.index_select(0, idx.to(torch.int64)))
+    r = (B - ax) if B is not None else -ax
+    if w is not None:
+        r = w.unsqueeze(1) * r
+    r = alpha * r
+    if C is not None:
+        r = C + r
+    return r if out is None else out.copy_(r)

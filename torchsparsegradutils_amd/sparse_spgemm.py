@@ -162,6 +162,21 @@ def _plan_for(aop: _Operand, bop: _Operand) -> _Plan:
     return cast(_Plan, plan)
 
 
+def _numeric(plan: _Plan, a: _pt.RowGather, a_val: torch.Tensor, b: _pt.RowGather, b_val: torch.Tensor) -> torch.Tensor:
+    """C's values on the pattern of `plan` for GPU operands on the patterns the plan was built from: the numeric kernel over the
+    plan's row bins, nothing else.  (Also what `SparseAMG.refresh` repeats on the plans it keeps, without a cache look-up.)"""
+    a_crow, a_col = _arrays(a)
+    b_crow, b_col = _arrays(b)
+    vals = torch.empty(plan.nnz, dtype=a_val.dtype, device=a_val.device)
+    acc = None
+    if plan.bins and plan.bins[-1][0] == len(_be.SPGEMM_BIN_LIMITS):
+        acc = vals if vals.dtype != torch.bfloat16 else torch.empty(plan.nnz, dtype=torch.float32, device=vals.device)
+    dims = (a.n_rows, a.n_cols, b.n_cols)
+    for bin_, rows in plan.bins:
+        _be.spgemm_numeric(bin_, rows, dims, a_crow, a_col, a_val, b_crow, b_col, b_val, plan.crow, plan.col, vals, acc=acc)
+    return vals
+
+
 def _cpu_plan(C: torch.Tensor, layout, idt) -> _Plan:
     """The pattern of a coalesced COO product on the CPU, in the result's layout and index dtype."""
     plan = _Plan()
@@ -192,15 +207,7 @@ class SparseSpGEMM(torch.autograd.Function):
             raise ValueError("sparse_spgemm: a row of B holds a column index more than once")
         if a_val.is_cuda:
             plan = _plan_for(aop, bop)
-            a_crow, a_col = _arrays(aop.plan)
-            b_crow, b_col = _arrays(bop.plan)
-            vals = torch.empty(plan.nnz, dtype=a_val.dtype, device=a_val.device)
-            acc = None
-            if plan.bins and plan.bins[-1][0] == len(_be.SPGEMM_BIN_LIMITS):
-                acc = vals if vals.dtype != torch.bfloat16 else torch.empty(plan.nnz, dtype=torch.float32, device=vals.device)
-            dims = (aop.n_rows, aop.n_cols, bop.n_cols)
-            for bin_, rows in plan.bins:
-                _be.spgemm_numeric(bin_, rows, dims, a_crow, a_col, a_val, b_crow, b_col, b_val, plan.crow, plan.col, vals, acc=acc)
+            vals = _numeric(plan, aop.plan, a_val, bop.plan, b_val)
         else:
             wide = torch.float32 if a_val.dtype == torch.bfloat16 else a_val.dtype
             C = _cpu.spgemm(_coo(aop, wide), _coo(bop, wide))
