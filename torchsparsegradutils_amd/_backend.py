@@ -282,6 +282,22 @@ SIGNATURES_AMG = {
 # header of csrc/ -> its table: bound by `load_library` after `ABI` and `STAGED` (tests/test_sparse_amg_cpu.py holds it against the header)
 STAGED_AMG = {"tsgu_hip_amg.h": SIGNATURES_AMG}
 
+# the additive entries of csrc/tsgu_hip_gmres.h (same library, same ABI version): the third STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI`, `STAGED` and `STAGED_AMG`)
+SIGNATURES_GMRES = {
+    "tsgu_gmres_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                   ctypes.POINTER(_i64)]),
+    "tsgu_gmres_project": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_gmres_subtract": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_gmres_scale": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_gmres_scalar": (_int, [_int, _int, _int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _int, _i64, _int, _ptr]),
+    "tsgu_gmres_update": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after `ABI`, `STAGED` and `STAGED_AMG` (tests/test_gmres_cpu.py holds it
+# against the header)
+STAGED_GMRES = {"tsgu_hip_gmres.h": SIGNATURES_GMRES}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -304,7 +320,7 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values()):
+        for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1760,6 +1776,28 @@ def coldot(X, Y):
         w = min(KRYLOV_SLAB, p - c0)
         launch("tsgu_coldot", dev, vt, n, w, X[:, c0:], ldx, Y[:, c0:], ldy, partial, out[c0:])
     return out
+
+
+def gmres_geometry(dtype: torch.dtype, n: int, p: int):
+    """(restart cap, basis group size, rows per workgroup, partial rows per launch) of the GMRES kernels for an (n, p) block
+    (csrc/tsgu_hip_gmres.h).  Host only; a width the lane geometry does not cover raises with the rule."""
+    fn = load_library().tsgu_gmres_geometry
+    cap, group, rows, parts = _int(0), _int(0), _i64(0), _i64(0)
+    rc = fn(_VTYPE[dtype], n, p, ctypes.byref(cap), ctypes.byref(group), ctypes.byref(rows), ctypes.byref(parts))
+    if rc == -3:
+        raise RuntimeError(f"gmres: {p} simultaneous right-hand sides are not supported by the fused kernels, which take "
+                           f"{krylov_width_rule(dtype)}")
+    check(rc, "tsgu_gmres_geometry")
+    return cap.value, group.value, rows.value, parts.value
+
+
+def gmres_state_rows(m: int) -> dict:
+    """First row of every field of the GMRES `scal` state for restart length m, and the row count (csrc/tsgu_hip_gmres.h)."""
+    return {"threshold": 0, "estimate": 1, "hnorm": 2, "g": 3, "cs": m + 4, "sn": 2 * m + 4, "y": 3 * m + 4, "h": 4 * m + 4,
+            "coef": 5 * m + 4, "R": 6 * m + 4, "rows": m * m + 6 * m + 4}
+
+
+GMRES_FLAG_WORDS = 4      # words in front of the per-column arrays of the GMRES `flags` (finished | cycle ended | steps | iterations)
 
 
 def device_copy(src: torch.Tensor, dst: torch.Tensor) -> None:

@@ -259,7 +259,9 @@ def sparse_generic_solve(
     r"""Solve :math:`A x = B` with an iterative ``solve(A, B, **kwargs)`` and sparsity-preserving
     gradients via the implicit function theorem.  ``A``: sparse COO/CSR ``(n, n)``; ``B``: dense
     ``(n,)`` or ``(n, k)``.  Defaults: both solvers ``None`` → ``minres``; one ``None`` → mirrored.
-    Mirrors reference ``sparse_solve.py:255-424``."""
+    Mirrors reference ``sparse_solve.py:255-424``.  For a nonsymmetric ``A`` the backward needs a solve with :math:`A^T`:
+    pass the pair ``solve=gmres, transpose_solve=gmres_t`` (``utils/gmres.py``); ``solve=gmres`` alone is mirrored to the
+    same solver, which is right only for symmetric ``A``."""
     if not isinstance(A, torch.Tensor) or not isinstance(B, torch.Tensor):
         raise ValueError("Both A and B should be instances of torch.Tensor")
     if A.layout not in (torch.sparse_coo, torch.sparse_csr):

@@ -8,6 +8,8 @@ from .linear_cg import linear_cg, LinearCGSettings
 from .minres import minres, MINRESSettings
 from .bicgstab import bicgstab, BICGSTABSettings
 from .lsmr import lsmr
+# restarted GMRES on the Arnoldi kernels (csrc/gmres.hip)
+from .gmres import gmres, gmres_t, GMRESSettings
 # the eigensolver loop on the tall-skinny kernels (csrc/lobpcg.hip)
 from .lobpcg import lobpcg
 
@@ -18,8 +20,8 @@ from .utils import sparse_block_diag, sparse_block_diag_split, stack_csr, sparse
 
 def last_solve_info(solver: str = "linear_cg"):
     """Iteration count / stopping outcome / final residual of the calling thread's most recent solve with
-    ``solver`` in {"linear_cg", "minres", "bicgstab"} (build extension: the reference only prints, see
-    utils/linear_cg.py:273-275)."""
+    ``solver`` in {"linear_cg", "minres", "bicgstab", "gmres"} (build extension: the reference only prints, see
+    utils/linear_cg.py:273-275).  For "gmres": ``iterations`` (inner steps per column), ``cycles``, ``restart``, ``fused``."""
     return _sys.modules[__name__ + "." + solver].last_solve_info()
 
 
