@@ -3,7 +3,8 @@
 Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_triangular_solve`` / ``sparse_generic_solve`` /
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
-``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_lobpcg`` beside them;
+``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
+``sparse_lobpcg`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -15,6 +16,7 @@ from .sparse_amg import SparseAMG, sparse_amg
 from .sparse_attention import SparseAttention, sparse_attention
 from .sparse_bsr_attention import SparseBSRAttention, sparse_bsr_attention
 from .sparse_bsr_mm import SparseBSRMatMul, sparse_bsr_mm
+from .sparse_coloring import SparseColoredIC0, SparseColoredILU0, SparseColoring, SparseSGS, sparse_coloring, sparse_sgs
 from .sparse_factor import SparseIC0, SparseILU0, sparse_ic0, sparse_ilu0
 from .sparse_fsai import SparseFSAI, sparse_fsai
 from .sparse_lobpcg import SparseLOBPCG, sparse_lobpcg
@@ -41,6 +43,12 @@ __all__ = [
     "sparse_ic0",
     "SparseILU0",
     "SparseIC0",
+    "sparse_coloring",
+    "SparseColoring",
+    "sparse_sgs",
+    "SparseSGS",
+    "SparseColoredILU0",
+    "SparseColoredIC0",
     "sparse_fsai",
     "SparseFSAI",
     "sparse_amg",

@@ -298,6 +298,20 @@ SIGNATURES_GMRES = {
 # against the header)
 STAGED_GMRES = {"tsgu_hip_gmres.h": SIGNATURES_GMRES}
 
+# the additive entries of csrc/tsgu_hip_color.h (same library, same ABI version): the fourth STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI`, `STAGED`, `STAGED_AMG` and `STAGED_GMRES`)
+SIGNATURES_COLOR = {
+    "tsgu_color_geometry": (_int, [ctypes.POINTER(_int)] * 6),
+    "tsgu_csr_color_round": (_int, [_int, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_csr_color_check": (_int, [_int, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _int, _int, _ptr]),
+    "tsgu_csr_color_sweep": (_int, [_int, _int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
+                                    _ptr, _ptr, _i64, _ptr, _i64, _ptr, _int, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_coloring_cpu.py holds it against
+# the header)
+STAGED_COLOR = {"tsgu_hip_color.h": SIGNATURES_COLOR}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -320,7 +334,8 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values()):
+        for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
+                      *STAGED_COLOR.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1628,6 +1643,111 @@ def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, 
            val if nnz else None, X if X.numel() else None, _ld(X), C, 0 if C is None else _ld(C), B, 0 if B is None else _ld(B), w,
            float(alpha), out if out.numel() else None, _ld(out))
     return out
+
+
+def color_geometry():
+    """(group widths of the colouring round and check, colours per window, group widths of the sweep, column tile of the sweep)
+    (csrc/tsgu_hip_color.h).  Host only."""
+    lo, hi, window, slo, shi, tile = _query("tsgu_color_geometry")
+    pows = lambda a, b: tuple(a << k for k in range(8) if (a << k) <= b)      # noqa: E731
+    return pows(lo, hi), window, pows(slo, shi), tile
+
+
+def _color_pattern(what: str, ptr, idx, tptr, tidx, n: int):
+    """The contiguous index arrays of a colouring call and the size of the transposed list."""
+    if ptr.numel() != n + 1 or ptr.dtype != idx.dtype or (tptr is None) != (tidx is None) or \
+            (tptr is not None and (tptr.numel() != n + 1 or tptr.dtype != ptr.dtype or tidx.dtype != ptr.dtype)):
+        raise RuntimeError(f"{what}: {n} rows need row pointers of {n + 1} words, all index arrays of one dtype")
+    ptr, idx = ptr.contiguous(), idx.contiguous()
+    if tptr is not None:
+        tptr, tidx = tptr.contiguous(), tidx.contiguous()
+    return ptr, idx, tptr, tidx, 0 if tidx is None else tidx.numel()
+
+
+def _color_vector(what: str, n: int, *vectors):
+    for c in vectors:
+        if c is not None and (c.dtype != torch.int32 or c.shape != (n,) or not c.is_contiguous()):
+            raise RuntimeError(f"{what}: colours are contiguous int32 vectors of {n} words")
+
+
+def csr_color_round(ptr, idx, tptr, tidx, colors, n: int, out, undecided, group: int = 8):
+    """One round of the greedy multicolouring on the pattern (ptr, idx) and its transpose (tptr, tidx; None when the pattern is
+    structurally symmetric) (csrc/tsgu_hip_color.h): `out` receives the colours after the round, `undecided` (an int64 word the
+    caller zeroed) becomes non-zero when a node stays uncoloured.  `group`: lanes per node, one of `color_geometry()[0]`."""
+    dev = require_device(ptr, idx, tptr, tidx, colors, out, undecided)
+    ptr, idx, tptr, tidx, nnz_t = _color_pattern("tsgu_csr_color_round", ptr, idx, tptr, tidx, n)
+    _color_vector("tsgu_csr_color_round", n, colors, out)
+    if undecided.dtype != torch.int64 or undecided.numel() != 1:
+        raise RuntimeError("tsgu_csr_color_round: `undecided` is one int64 word")
+    nnz = idx.numel()
+    launch("tsgu_csr_color_round", dev, itype_of(ptr), n, nnz, ptr, idx if nnz else None, nnz_t, tptr, tidx if nnz_t else None,
+           colors, out, undecided, int(group))
+    return out
+
+
+def csr_color_check(ptr, idx, tptr, tidx, colors, n: int, n_colors: int, group: int = 8):
+    """A device int64: 0 when `colors` is a colouring of the pattern with `n_colors` colours, else 1 + the lowest row whose colour
+    is outside [0, n_colors) or held by a neighbour (csrc/tsgu_hip_color.h).  Nothing is read back here."""
+    dev = require_device(ptr, idx, tptr, tidx, colors)
+    ptr, idx, tptr, tidx, nnz_t = _color_pattern("tsgu_csr_color_check", ptr, idx, tptr, tidx, n)
+    _color_vector("tsgu_csr_color_check", n, colors)
+    first = torch.zeros((), dtype=torch.int64, device=dev)
+    nnz = idx.numel()
+    launch("tsgu_csr_color_check", dev, itype_of(ptr), n, nnz, ptr, idx if nnz else None, nnz_t, tptr, tidx if nnz_t else None,
+           colors if n else None, int(n_colors), first, int(group))
+    return first
+
+
+SWEEP_DIVIDE, SWEEP_UNIT, SWEEP_SCALED = 0, 1, 2
+
+
+def csr_color_sweeps(mode: int, begin, end, idx, diag, val, B, X, classes, vmap=None, bmap=None, out=None, out_rows=None, group: int = 8):
+    """One triangular sweep by colour classes, in place in the workspace X (n, p): one launch of `tsgu_csr_color_sweep`
+    (csrc/tsgu_hip_color.h) per (row0, row1) of `classes`, in their order.  For the rows of a class,
+    x[i] = (B[bmap(i)] − Σ_{e in [begin[i], end[i])} val[vmap(e)]·x[idx[e]]) / val[vmap(diag[i])] (SWEEP_DIVIDE), without the division
+    (SWEEP_UNIT, diag None) or with the sum alone divided (SWEEP_SCALED); `out`, when given, also receives x[i] in row out_rows(i).
+    The operands are checked once for all classes and nothing is copied: they are contiguous in the way the plan made them."""
+    n, p = X.shape
+    idt = begin.dtype
+    if (begin.numel() != n or end.numel() != n or B.dim() != 2 or B.size(0) != n or B.size(1) != p or B.dtype != val.dtype
+            or X.dtype != val.dtype or idx.dtype != idt or end.dtype != idt
+            or any(t is not None and (t.numel() != n or t.dtype != idt) for t in (diag, bmap, out_rows))
+            or (vmap is not None and (vmap.numel() != idx.numel() or vmap.dtype != idt))
+            or (out is not None and (out.shape != X.shape or out.dtype != val.dtype))
+            or any(t is not None and not (t.is_cuda and t.device == X.device)
+                   for t in (begin, end, idx, diag, val, B, X, vmap, bmap, out, out_rows))
+            or any(t is not None and not t.is_contiguous() for t in (begin, end, idx, diag, val, vmap, bmap, out_rows))
+            or any(t is not None and ((t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1))) for t in (B, X, out))):
+        raise RuntimeError(f"tsgu_csr_color_sweep: {n} rows need contiguous begin, end, diag, bmap and out_rows of {n} words and a vmap of "
+                           "as many words as columns, all of one index dtype, and row-major B, X and out of (n, p) elements of the "
+                           "values' dtype, all on one GPU")
+    dev = X.device
+    fn = getattr(_lib or load_library(), "tsgu_csr_color_sweep")
+    head = (_VTYPE.get(val.dtype, -1), itype_of(begin), int(mode), n, idx.numel(), val.numel())
+    tail = (p, begin.data_ptr(), end.data_ptr(), idx.data_ptr() if idx.numel() else None, _p(diag), _p(vmap),
+            val.data_ptr() if val.numel() else None, B.data_ptr(), _ld(B), _p(bmap), X.data_ptr(), _ld(X), _p(out),
+            0 if out is None else _ld(out), _p(out_rows), int(group), dev.index)
+
+    def run():
+        stream = _raw_stream(dev)          # (read at call time: the same code runs eagerly and under graph capture)
+        for row0, row1 in classes:
+            rc = fn(*head, int(row0), int(row1), *tail, stream)
+            if rc:
+                check(rc, "tsgu_csr_color_sweep")
+
+    if torch.cuda.current_device() == dev.index:
+        run()
+    else:
+        with torch.cuda.device(dev):
+            run()
+    return X
+
+
+def csr_color_sweep(mode: int, begin, end, idx, diag, val, B, X, row0: int, row1: int, vmap=None, bmap=None, out=None, out_rows=None,
+                    group: int = 8):
+    """The rows [row0, row1) of ONE colour class: `csr_color_sweeps` with a single class."""
+    return csr_color_sweeps(mode, begin, end, idx, diag, val, B, X, ((row0, row1),), vmap=vmap, bmap=bmap, out=out, out_rows=out_rows,
+                            group=group)
 
 
 _PENDING = []            # (event or None, pinned / host int32 slot, what, tsgu status)

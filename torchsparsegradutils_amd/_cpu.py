@@ -689,3 +689,92 @@ def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, 
     if C is not None:
         r = C + r
     return r if out is None else out.copy_(r)
+
+
+# ---- the primitives of the multicolour ordering (sparse_coloring.py): csrc/tsgu_hip_color.h in torch ops --------------------------
+
+def _color_edges(ptr, idx, tptr, tidx, n: int):
+    """(u, v) int64: every stored entry (u, v) of A and, when given, of Aᵀ, without the diagonal and the columns outside the matrix."""
+    u, v = _rows_of(ptr, idx.numel()), idx.to(torch.int64)
+    if tptr is not None:
+        u, v = torch.cat((u, _rows_of(tptr, tidx.numel()))), torch.cat((v, tidx.to(torch.int64)))
+    else:
+        u, v = torch.cat((u, v)), torch.cat((v, u))
+    keep = (u != v) & (v >= 0) & (v < n) & (u >= 0) & (u < n)
+    return u[keep], v[keep]
+
+
+def color_greedy(ptr, idx, tptr, tidx, n: int) -> torch.Tensor:
+    """The colouring of csrc/tsgu_hip_color.h by its own rounds: an uncoloured node with no uncoloured neighbour of greater key
+    (lowbias32(i), i) takes the smallest colour no neighbour holds.  int32 colours; reference speed only."""
+    _cpu_only(ptr, idx, tptr, tidx)
+    u, v = _color_edges(ptr, idx, tptr, tidx, n)
+    ar = torch.arange(n, dtype=torch.int64)
+    key = _lowbias32(ar) * (1 << 31) + ar
+    up = key[v] > key[u]
+    colors = torch.full((n,), -1, dtype=torch.int64)
+    for _ in range(n + 1):
+        unc = colors < 0
+        if not bool(unc.any()):
+            break
+        blocked = torch.zeros(n, dtype=torch.bool)
+        blocked[u[up & unc[v]]] = True
+        ready = unc & ~blocked
+        live = ready[u] & (colors[v] >= 0)
+        lu, lc = u[live], colors[v[live]]
+        cand = torch.zeros(n, dtype=torch.int64)
+        while True:
+            hit = lu[lc == cand[lu]]
+            if hit.numel() == 0:
+                break
+            cand[torch.unique(hit)] += 1
+        colors = torch.where(ready, cand, colors)
+    return colors.to(torch.int32)
+
+
+def color_check(ptr, idx, tptr, tidx, colors, n: int, n_colors: int) -> torch.Tensor:
+    """An int64 scalar: 0 for a colouring with `n_colors` colours, else 1 + the lowest row whose colour is outside [0, n_colors) or
+    held by a neighbour."""
+    _cpu_only(ptr, idx, tptr, tidx, colors)
+    u, v = _color_edges(ptr, idx, tptr, tidx, n)
+    c = colors.to(torch.int64)
+    bad = (c < 0) | (c >= n_colors)
+    bad[u[c[u] == c[v]]] = True
+    rows = torch.nonzero(bad).reshape(-1)
+    return rows[:1].sum() + 1 if rows.numel() else torch.zeros((), dtype=torch.int64)
+
+
+def csr_color_sweep(mode: int, begin, end, idx, diag, val, B, X, row0: int, row1: int, vmap=None, bmap=None, out=None, out_rows=None,
+                    group: int = 8) -> torch.Tensor:
+    """The rows [row0, row1) of one colour class of a triangular sweep, in place in X, as `_backend.csr_color_sweep`; a row is
+    summed in entry order (``index_add_``) in the value type."""
+    _cpu_only(begin, end, idx, diag, val, B, X, vmap, bmap, out, out_rows)
+    if row1 <= row0:
+        return X
+    rows = torch.arange(row0, row1, dtype=torch.int64)
+    s, e = begin[row0:row1].to(torch.int64), end[row0:row1].to(torch.int64)
+    lens = (e - s).clamp_(min=0)
+    total = int(lens.sum())
+    local = torch.repeat_interleave(torch.arange(row1 - row0, dtype=torch.int64), lens, output_size=total)
+    ent = s[local] + (torch.arange(total, dtype=torch.int64) - (torch.cumsum(lens, 0) - lens)[local])
+    q = ent if vmap is None else vmap.to(torch.int64)[ent]
+    acc = torch.zeros((row1 - row0, X.size(1)), dtype=val.dtype)
+    acc.index_add_(0, local, val[q].unsqueeze(1) * X[idx.to(torch.int64)[ent]])
+    rhs = B[rows if bmap is None else bmap.to(torch.int64)[rows]]
+    if mode == 1:
+        r = rhs - acc
+    else:
+        dq = diag.to(torch.int64)[rows]
+        d = val[dq if vmap is None else vmap.to(torch.int64)[dq]].unsqueeze(1)
+        r = (rhs - acc) / d if mode == 0 else rhs - acc / d
+    X[rows] = r
+    if out is not None:
+        out[rows if out_rows is None else out_rows.to(torch.int64)[rows]] = r
+    return X
+
+
+def csr_color_sweeps(mode: int, begin, end, idx, diag, val, B, X, classes, vmap=None, bmap=None, out=None, out_rows=None, group: int = 8):
+    """One triangular sweep by colour classes, as `_backend.csr_color_sweeps`."""
+    for row0, row1 in classes:
+        csr_color_sweep(mode, begin, end, idx, diag, val, B, X, row0, row1, vmap=vmap, bmap=bmap, out=out, out_rows=out_rows)
+    return X

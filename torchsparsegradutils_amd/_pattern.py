@@ -1234,3 +1234,192 @@ def fsai_plan(g: RowGather, capacity: int) -> FsaiPlan:
         raise ValueError(f"sparse_fsai: row {row} of the pattern stores {m} lower-triangular entries, more than the {capacity} a local "
                          "system may have (a row costs m³: choose a sparser pattern)")
     return plan
+
+
+# ---- multicolour ordering (sparse_coloring.py) ---------------------------------------------------------------------------------------
+_COLOR_POLL_ROUNDS = 4       # colouring rounds between two reads of the "still undecided" word
+
+
+class SweepTable:
+    """One triangle of a pattern as the colour sweep takes it (csrc/tsgu_hip_color.h): per-row `begin` / `end` positions into `idx`
+    and the diagonal's position `diag`, all contiguous and of one index dtype."""
+
+    __slots__ = ("begin", "end", "idx", "diag")
+
+    def __init__(self, begin, end, idx, diag):
+        self.begin, self.end, self.idx, self.diag = begin.contiguous(), end.contiguous(), idx.contiguous(), diag.contiguous()
+
+
+def sweep_tables(crow, col, diag_pos):
+    """(lower, upper) SweepTables of a CSR pattern with ascending columns and the diagonal at `diag_pos`: the strict triangles are
+    the entries before and after it.  Nothing is split."""
+    idt = col.dtype
+    crow, diag_pos = crow.to(idt), diag_pos.to(idt)
+    return SweepTable(crow[:-1], diag_pos, col, diag_pos), SweepTable(diag_pos + 1, crow[1:], col, diag_pos)
+
+
+class ColoringPlan:
+    """A multicolour ordering of a square pattern (``coloring_plan``).
+
+    colors     (n,) int32, the colour of every row;  n_colors  their number
+    perm       (n,) int64, new → old: the rows ordered by (colour, old index);  inverse  old → new
+    offsets    n_colors + 1 host integers: class c is the new rows [offsets[c], offsets[c + 1])
+    gather     the RowGather of P·A·Pᵀ with ascending columns
+    pos        (nnz,) int64: position in A's value array of every entry of the permuted pattern
+    ``factor`` its FactorPlan (diagonal positions), ``transposed()`` the pattern of (P·A·Pᵀ)ᵀ with its value map and diagonal
+    positions, ``tables()`` / ``lower_tables()`` the SweepTables of the combined and of the lower-triangular arrays, ``index(t)``
+    a vector in the pattern's index dtype — all derived on first use."""
+
+    __slots__ = ("colors", "n_colors", "perm", "inverse", "offsets", "gather", "pos", "_parts")
+
+    def __init__(self, colors, n_colors, perm, inverse, offsets, gather, pos):
+        self.colors, self.n_colors, self.perm, self.inverse, self.offsets = colors, n_colors, perm, inverse, offsets
+        self.gather, self.pos = gather, pos
+        self._parts = {}
+
+    def _part(self, key, build):
+        got = self._parts.get(key)
+        if got is None:
+            got = self._parts[key] = build()
+        return got
+
+    @property
+    def factor(self) -> FactorPlan:
+        return factor_plan(self.gather)
+
+    @property
+    def classes(self):
+        """((row0, row1) of class 0, of class 1, …) in the new numbering."""
+        return self._part("classes", lambda: tuple(zip(self.offsets[:-1], self.offsets[1:])))
+
+    @property
+    def perm_index(self):
+        """`perm` in the index dtype of the pattern: the row maps of the first and the last sweep."""
+        return self._part("perm_index", lambda: self.perm.to(self.gather.col.dtype).contiguous())
+
+    @property
+    def pos_index(self):
+        return self._part("pos_index", lambda: self.pos.to(self.gather.col.dtype).contiguous())
+
+    def tables(self):
+        """(lower, upper) SweepTables of the combined arrays of P·A·Pᵀ."""
+        return self._part("tables", lambda: sweep_tables(self.gather.crow, self.gather.col, self.factor.diag_pos))
+
+    def transposed(self):
+        """(RowGather of (P·A·Pᵀ)ᵀ — its ``perm`` gathers the permuted values —, (lower, upper) SweepTables of it)."""
+        def build():
+            tg = self.gather.transposed
+            diag = torch.nonzero(tg.row_indices() == tg.col).reshape(-1)
+            return tg, sweep_tables(tg.crow, tg.col, diag)
+        return self._part("transposed", build)
+
+    def lower_tables(self):
+        """For IC(0): (RowGather of tril(P·A·Pᵀ), its positions in the permuted arrays, the SweepTable of L, the SweepTable of Lᵀ,
+        the map that gathers Lᵀ's values from L's)."""
+        def build():
+            lg, lpos, dp = self.factor.lower()
+            lt = lg.transposed                                # (ascending columns: the diagonal opens every row of Lᵀ)
+            idt = lg.col.dtype
+            head = lt.crow[:-1].to(idt)
+            return (lg, lpos, SweepTable(lg.crow[:-1].to(idt), dp.to(idt), lg.col, dp.to(idt)),
+                    SweepTable(head + 1, lt.crow[1:].to(idt), lt.col, head), lt.perm.to(torch.int64))
+        return self._part("lower", build)
+
+
+def _color_lists(g: RowGather):
+    """(ptr, idx, tptr, tidx) of the colouring: the transposed lists are None when the pattern is structurally symmetric (decided
+    with one host read; a pattern whose columns are not sorted may be taken for unsymmetric, which costs time only)."""
+    idt = g.col.dtype
+    ptr = g.crow if g.crow.dtype == idt else g.crow.to(idt)
+    t = g.transposed
+    tptr = t.crow if t.crow.dtype == idt else t.crow.to(idt)
+    if bool(torch.equal(ptr, tptr) and torch.equal(g.col, t.col)):
+        return ptr.contiguous(), g.col.contiguous(), None, None
+    return ptr.contiguous(), g.col.contiguous(), tptr.contiguous(), t.col.contiguous()
+
+
+def greedy_colors(g: RowGather, group: Optional[int] = None) -> torch.Tensor:
+    """The colours of the pattern (int32) by the rounds of csrc/tsgu_hip_color.h; `group`: lanes per node (the result is the same)."""
+    from . import _backend as _be
+
+    n, dev = g.n_rows, g.col.device
+    ptr, idx, tptr, tidx = _color_lists(g)
+    if dev.type != "cuda":
+        from . import _cpu
+
+        return _cpu.color_greedy(ptr, idx, tptr, tidx, n)
+    if group is None:
+        widths = _be.color_geometry()[0]
+        per_row = idx.numel() * (1 if tidx is None else 2)
+        group = next((w for w in widths if w * max(n, 1) >= per_row), widths[-1])
+    a = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    b = torch.empty_like(a)
+    undecided = torch.zeros((), dtype=torch.int64, device=dev)
+    rounds = 0
+    while n:
+        for _ in range(_COLOR_POLL_ROUNDS):       # (a round with nothing uncoloured changes nothing: polling every few rounds is exact)
+            undecided.zero_()
+            _be.csr_color_round(ptr, idx, tptr, tidx, a, n, b, undecided, group)
+            a, b = b, a
+        rounds += _COLOR_POLL_ROUNDS
+        if not int(undecided.item()):
+            break
+        if rounds > n + _COLOR_POLL_ROUNDS:
+            raise RuntimeError("sparse_coloring: the colouring rounds did not finish")
+    return a
+
+
+def check_colors(g: RowGather, colors: torch.Tensor, n_colors: int) -> int:
+    """0, or 1 + the lowest row of `colors` (int32) that clashes with a neighbour or lies outside [0, n_colors): one host read."""
+    ptr, idx, tptr, tidx = _color_lists(g)
+    if colors.is_cuda:
+        from . import _backend as _be
+
+        return int(_be.csr_color_check(ptr, idx, tptr, tidx, colors, g.n_rows, n_colors).item())
+    from . import _cpu
+
+    return int(_cpu.color_check(ptr, idx, tptr, tidx, colors, g.n_rows, n_colors).item())
+
+
+def coloring_plan(g: RowGather, colors=None) -> ColoringPlan:
+    """The ColoringPlan of a 2-D square pattern: the greedy colouring of csrc/tsgu_hip_color.h (cached with the pattern), or the
+    caller's `colors` (validated: ValueError naming the lowest conflicting row; not cached).  Torch ops and a handful of host reads
+    at plan time; none of it is hot."""
+    if g.batch is not None or g.n_rows != g.n_cols:
+        raise ValueError("coloring_plan: a 2-D square pattern is required")
+    if colors is None:
+        plan = g.core.own.get("coloring")
+        if plan is not None:
+            return plan
+    n, dev = g.n_rows, g.col.device
+    if colors is None:
+        c = greedy_colors(g)
+    else:
+        c = colors.detach().reshape(-1)
+        if c.numel() != n or c.dtype.is_floating_point or c.dtype == torch.bool or c.device != dev:
+            raise ValueError(f"sparse_coloring: colors must be {n} integers on the device of A")
+        lo, hi = (int(v) for v in torch.stack((c.min(), c.max())).tolist()) if n else (0, -1)
+        if lo < 0 or hi >= 2 ** 31 - 1:
+            raise ValueError("sparse_coloring: colors must be non-negative 32-bit integers")
+        c = c.to(torch.int32).contiguous()
+        bad = check_colors(g, c, hi + 1)
+        if bad:
+            raise ValueError(f"sparse_coloring: colors is not a colouring of A: row {bad - 1} has a neighbour of its own colour")
+    c64 = c.to(torch.int64)
+    counts = torch.bincount(c64).tolist() if n else []          # (one host read: the number of colours and the class sizes)
+    offsets = [0]
+    for k in counts:
+        offsets.append(offsets[-1] + int(k))
+    perm = torch.argsort(c64, stable=True)
+    inverse = torch.empty_like(perm)
+    inverse[perm] = torch.arange(n, dtype=torch.int64, device=dev)
+    rows, col = inverse[g.row_indices().to(torch.int64)], inverse[g.col.to(torch.int64)]
+    order = torch.argsort(rows * n + col, stable=True)
+    idt = g.col.dtype
+    crow = torch.zeros(n + 1, dtype=idt, device=dev)
+    crow[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
+    pos = order if g.perm is None else g.perm.to(torch.int64)[order]
+    plan = ColoringPlan(c, len(counts), perm, inverse, tuple(offsets), RowGather(crow, col[order].to(idt).contiguous(), n, n), pos)
+    if colors is None:
+        g.core.own["coloring"] = plan
+    return plan

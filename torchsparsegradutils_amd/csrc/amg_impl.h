@@ -99,8 +99,8 @@ __device__ __forceinline__ unsigned amg_lowbias32(unsigned x) {
 }
 
 // mode 0: the initial keys.  mode 1: one round's decision, and `undecided` != 0 when a node is still undecided after it.
-// mode 2: the root's own key for roots, 0 otherwise.
-__global__ __launch_bounds__(kBlock) void amg_mis2_kernel(int mode, int64_t n, const unsigned long long* key, const unsigned long long* t,
+// mode 2: the root's own key for roots, 0 otherwise.  (Internal linkage: color_impl.h includes this header for the row walk and the hash.)
+static __global__ __launch_bounds__(kBlock) void amg_mis2_kernel(int mode, int64_t n, const unsigned long long* key, const unsigned long long* t,
                                                           unsigned long long* out, unsigned long long* undecided) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;

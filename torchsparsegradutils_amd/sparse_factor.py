@@ -169,7 +169,7 @@ class SparseIC0(_Factor):
         return torch.sparse_csr_tensor(self._gather.crow, self._gather.col, self.values, self.shape)
 
 
-def sparse_ilu0(A: torch.Tensor, *, shift: float = 0.0, check: bool = True) -> SparseILU0:
+def sparse_ilu0(A: torch.Tensor, *, shift: float = 0.0, check: bool = True, ordering=None) -> SparseILU0:
     r"""ILU(0) of a square sparse ``A`` (COO or CSR, float32 / float64): ``A ≈ L·U`` with no entry outside the pattern of ``A``.
 
     The IKJ form; every update is one IEEE division, multiplication and subtraction in the value type, applied in ascending order
@@ -177,7 +177,15 @@ def sparse_ilu0(A: torch.Tensor, *, shift: float = 0.0, check: bool = True) -> S
     store every diagonal entry and no column twice per row (``ValueError`` naming the first offending row); unsorted columns are
     sorted through a cached permutation.  ``shift``: the diagonal used is ``a_ii·(1 + shift)``.  ``check=True`` reads the
     breakdown word (one synchronisation) and raises ``RuntimeError("zero pivot in row r")``; ``check=False`` leaves ``.info`` on
-    the device.  No gradient flows through the factor (see the module's docstring)."""
+    the device.  No gradient flows through the factor (see the module's docstring).
+
+    ``ordering=None`` is the natural ordering.  ``ordering="multicolor"`` (or a ``SparseColoring``) factorises ``P·A·Pᵀ`` in a
+    multicolour ordering instead and returns a ``SparseColoredILU0``, whose application is one wait-free launch per colour and sweep
+    (``sparse_coloring.py``): a far cheaper application of a weaker preconditioner."""
+    if ordering is not None:
+        from .sparse_coloring import colored_ilu0
+
+        return colored_ilu0(A, ordering, shift, check)
     with torch.no_grad():
         g, values = _operand(A, "sparse_ilu0")
         plan = _pt.factor_plan(g)
@@ -187,12 +195,17 @@ def sparse_ilu0(A: torch.Tensor, *, shift: float = 0.0, check: bool = True) -> S
     return SparseILU0(plan, out, info, A.shape)
 
 
-def sparse_ic0(A: torch.Tensor, *, shift: float = 0.0, check: bool = True) -> SparseIC0:
+def sparse_ic0(A: torch.Tensor, *, shift: float = 0.0, check: bool = True, ordering=None) -> SparseIC0:
     r"""IC(0) of a square sparse ``A`` (COO or CSR, float32 / float64): ``A ≈ L·Lᵀ`` with ``L`` on the pattern of ``tril(A)``.
 
     Only the lower triangle of ``A`` is read; symmetry is not checked.  The pattern conditions and ``shift`` (the usual remedy for
     a breakdown) are those of :func:`sparse_ilu0`.  Two calls give the same bits.  ``check=True`` raises
-    ``RuntimeError("non-positive pivot in row r")``.  No gradient flows through the factor."""
+    ``RuntimeError("non-positive pivot in row r")``.  No gradient flows through the factor.  ``ordering``: as for
+    :func:`sparse_ilu0`; the coloured form is a ``SparseColoredIC0``."""
+    if ordering is not None:
+        from .sparse_coloring import colored_ic0
+
+        return colored_ic0(A, ordering, shift, check)
     with torch.no_grad():
         g, values = _operand(A, "sparse_ic0")
         plan = _pt.factor_plan(g)
