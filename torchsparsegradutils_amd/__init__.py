@@ -4,7 +4,7 @@ Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_tria
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
 ``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
-``sparse_lobpcg`` beside them;
+``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -20,6 +20,7 @@ from .sparse_coloring import SparseColoredIC0, SparseColoredILU0, SparseColoring
 from .sparse_factor import SparseIC0, SparseILU0, sparse_ic0, sparse_ilu0
 from .sparse_fsai import SparseFSAI, sparse_fsai
 from .sparse_lobpcg import SparseLOBPCG, sparse_lobpcg
+from .sparse_logdet import SparseLogDet, sparse_inv_quad_logdet, sparse_logdet
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
@@ -55,6 +56,9 @@ __all__ = [
     "SparseAMG",
     "sparse_lobpcg",
     "SparseLOBPCG",
+    "sparse_logdet",
+    "sparse_inv_quad_logdet",
+    "SparseLogDet",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",

@@ -312,6 +312,18 @@ SIGNATURES_COLOR = {
 # the header)
 STAGED_COLOR = {"tsgu_hip_color.h": SIGNATURES_COLOR}
 
+# the additive entries of csrc/tsgu_hip_quadrature.h (same library, same ABI version): the fifth STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI` and the four registries above)
+SIGNATURES_QUADRATURE = {
+    "tsgu_quadrature_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_i64)]),
+    "tsgu_tridiag_quadrature": (_int, [_int, _int, _int, _int, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_rademacher_fill": (_int, [_int, _i64, _i64, _i64, _ptr, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_logdet_cpu.py holds it
+# against the header)
+STAGED_QUADRATURE = {"tsgu_hip_quadrature.h": SIGNATURES_QUADRATURE}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -335,7 +347,7 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
-                      *STAGED_COLOR.values()):
+                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -2092,3 +2104,55 @@ def csr_row_sumsq_backward(crow, col, perm, val, w, g, n_rows: int):
     launch("tsgu_csr_row_sumsq_backward", dev, vtype_of(val), itype_of(crow), n_rows, val.numel(), w.numel() if w is not None else 0, crow, col,
            perm, val, w, g, grad)
     return grad
+
+
+# ---- Lanczos quadrature and Rademacher probes (csrc/tsgu_hip_quadrature.h; sparse_logdet.py) ------------------------------------
+QUAD_CG, QUAD_ENTRIES = 0, 1                                   # `kind`: rows of CG coefficients | rows of (diagonal, off-diagonal)
+QUAD_LOG, QUAD_RECIPROCAL, QUAD_IDENTITY, QUAD_ONE = 0, 1, 2, 3  # `fn`
+QUAD_NO_WORK_ROWS = 64                                         # the header's promise: r up to here never reads `work`
+
+
+@functools.lru_cache(maxsize=None)
+def quadrature_geometry():
+    """(steps_cap, work_bytes_per_column) of tsgu_tridiag_quadrature.  Host only."""
+    return _query("tsgu_quadrature_geometry")
+
+
+def tridiag_quadrature(coef, kind: int = QUAD_CG, fn: int = QUAD_LOG, scale=None, p: int = None):
+    """(out, info) of tsgu_tridiag_quadrature for the first `p` columns (default: all) of the contiguous [r][2][width] array `coef`
+    of float32 or float64: out[c] = scale[c]·Σ_j τ_j² f(λ_j) in coef's dtype, info[c] = ±r_c (int32).  One launch, no host read."""
+    dev = require_device(coef, scale)
+    if coef.dim() != 3 or coef.size(1) != 2 or not coef.is_contiguous():
+        raise RuntimeError(f"tsgu_tridiag_quadrature: coef must be a contiguous [r][2][p] array, got {tuple(coef.shape)}")
+    r, width = coef.size(0), coef.size(2)
+    p = width if p is None else int(p)
+    if not 0 < p <= width:
+        raise RuntimeError(f"tsgu_tridiag_quadrature: {p} columns asked of an array of {width}")
+    if p != width:
+        # (the kernel takes a dense [r][2][p] array: the leading columns of a wider history are packed first)
+        coef = coef[:, :, :p].contiguous()
+    if scale is not None:
+        scale = scale.contiguous()
+        if scale.dtype != coef.dtype or scale.numel() != p:
+            raise RuntimeError(f"tsgu_tridiag_quadrature: scale must hold {p} values of {coef.dtype}")
+    out = torch.empty(p, dtype=coef.dtype, device=dev)
+    info = torch.empty(p, dtype=torch.int32, device=dev)
+    work = None
+    if r > QUAD_NO_WORK_ROWS:
+        work = torch.empty(p * quadrature_geometry()[1] // 8, dtype=torch.float64, device=dev)
+    launch("tsgu_tridiag_quadrature", dev, vtype_of(coef), int(kind), int(fn), r, p, coef, scale, out, info, work)
+    return out, info
+
+
+def rademacher_fill(n: int, p: int, seed: int, dtype: torch.dtype, device) -> torch.Tensor:
+    """The (n, p) block of ±1 of tsgu_rademacher_fill: a pure function of (seed, row, column), the same bits as `_cpu.rademacher_fill`."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        from . import _cpu
+
+        return _cpu.rademacher_fill(n, p, seed, dtype)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty((n, p), dtype=dtype, device=device)
+    launch("tsgu_rademacher_fill", device, vtype_of(out), n, p, _i64(int(seed)).value, out)
+    return out

@@ -778,3 +778,95 @@ def csr_color_sweeps(mode: int, begin, end, idx, diag, val, B, X, classes, vmap=
     for row0, row1 in classes:
         csr_color_sweep(mode, begin, end, idx, diag, val, B, X, row0, row1, vmap=vmap, bmap=bmap, out=out, out_rows=out_rows)
     return X
+
+
+# ---- Lanczos quadrature (sparse_logdet.py): csrc/tsgu_hip_quadrature.h in torch ops ------------------------------------------------
+
+def rademacher_fill(n: int, p: int, seed: int, dtype: torch.dtype) -> torch.Tensor:
+    """The (n, p) block of ±1 of tsgu_rademacher_fill, bit for bit: the sign bit of lowbias32(c + lowbias32(i + s)) with
+    s = lowbias32(lo32(seed) ^ lowbias32(hi32(seed))) and sums modulo 2^32."""
+    m = 0xFFFFFFFF
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s = _lowbias32(torch.tensor(seed & m, dtype=torch.int64) ^ _lowbias32(torch.tensor(seed >> 32, dtype=torch.int64)))
+    rows = _lowbias32((torch.arange(n, dtype=torch.int64) + s) & m)
+    h = _lowbias32((torch.arange(p, dtype=torch.int64).unsqueeze(0) + rows.unsqueeze(1)) & m)
+    return torch.where((h >> 31) != 0, -1.0, 1.0).to(dtype)
+
+
+def cg_history_loop(matmul, dot, rhs: torch.Tensor, n_hist: int, tolerance: float, max_iter: int, eps: float, stop_after: float):
+    """Conjugate gradients from x = 0 on the normalised columns `rhs` (n, p) with every column's coefficients kept:
+    (x, hist [n_hist][2][p] of (alpha, beta), iterations, residual norms (p,), tolerance reached).  The recurrences, guards and the
+    stop rule are those of `linear_cg._two_launch_loop` (alpha = 0 for a column whose residual fell below `stop_after` or whose
+    p'Ap is below `eps`; the mean residual norm is tested from iteration max(min(10, max_iter - 1), min(n_hist, max_iter - 1)) on),
+    written in torch ops around the closures `matmul` (v -> A v) and `dot` (column-wise dot products): CPU operands, and the GPU
+    solves the fused loop declines."""
+    p = rhs.size(1)
+    x = torch.zeros_like(rhs)
+    r = rhs.clone()
+    pv = r.clone()
+    rr = dot(r, r)
+    hist = torch.zeros((n_hist, 2, p), dtype=rhs.dtype, device=rhs.device)
+    rnorm = rr.sqrt()
+    frozen = rnorm < stop_after
+    floor = max(min(10, max_iter - 1), min(n_hist, max_iter - 1))
+    one, zero = torch.ones_like(rr), torch.zeros_like(rr)
+    iters, done = 0, False
+    for k in range(max_iter):
+        Ap = matmul(pv)
+        pap = dot(pv, Ap)
+        ok = (pap >= eps) & ~frozen
+        alpha = torch.where(ok, rr / torch.where(ok, pap, one), zero)
+        x = torch.addcmul(x, alpha.unsqueeze(0), pv)
+        r = torch.addcmul(r, alpha.unsqueeze(0), Ap, value=-1)
+        rr_new = dot(r, r)
+        ok = rr >= eps
+        beta = torch.where(ok, rr_new / torch.where(ok, rr, one), zero)
+        if k < n_hist:
+            hist[k, 0], hist[k, 1] = alpha, beta
+        pv = torch.addcmul(r, beta.unsqueeze(0), pv)
+        rr = rr_new
+        rnorm = rr.sqrt()
+        frozen = rnorm < stop_after
+        iters = k + 1
+        if k >= floor and bool(rnorm.mean() < tolerance):
+            done = True
+            break
+    return x, hist, iters, rnorm, done
+
+
+def tridiag_quadrature(coef: torch.Tensor, kind: int = 0, fn: int = 0, scale=None, p: int = None):
+    """(out, info) of tsgu_tridiag_quadrature in torch ops: the same entries, the same per-column length rule, `torch.linalg.eigh`
+    in float64.  out in coef's dtype, info int32."""
+    _cpu_only(coef, scale)
+    r, width = coef.size(0), coef.size(2)
+    p = width if p is None else int(p)
+    c64 = coef[:, :, :p].to(torch.float64)
+    out = torch.zeros(p, dtype=torch.float64)
+    info = torch.zeros(p, dtype=torch.int32)
+    for c in range(p):
+        a, b = c64[:, 0, c], c64[:, 1, c]
+        if kind == 0:
+            bad_a = ~((a > 0) & torch.isfinite(a))
+            bad_b = ~((b > 0) & torch.isfinite(b))
+            n = int(bad_a.nonzero()[0]) if bool(bad_a.any()) else r
+            if bool(bad_b[:n].any()):
+                n = min(n, int(bad_b.nonzero()[0]) + 1)
+            ia = 1.0 / a[:n]
+            d = ia.clone()
+            d[1:] += (b[:n] * ia)[:-1]
+            e = (b[:n].sqrt() * ia)[:-1]
+        else:
+            bad_b = (b == 0) | ~torch.isfinite(b)
+            n = int(bad_b.nonzero()[0]) + 1 if bool(bad_b.any()) else r
+            d, e = a[:n], b[: n - 1]
+        if n == 0:
+            continue
+        lam, vec = torch.linalg.eigh(torch.diag(d) + torch.diag(e, 1) + torch.diag(e, -1))
+        w = vec[0] ** 2
+        f = (lam.log(), lam.reciprocal(), lam, torch.ones_like(lam))[fn]
+        bad = fn <= 1 and bool((lam <= 0).any())
+        out[c] = float("nan") if bad else (w * f).sum()
+        info[c] = -n if bad else n
+    if scale is not None:
+        out = out * scale.to(torch.float64)
+    return out.to(coef.dtype), info

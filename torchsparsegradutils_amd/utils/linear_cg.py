@@ -167,16 +167,7 @@ def linear_cg(
     result = result.mul(rhs_norm)
 
     if not tolerance_reached and n_iter > 0:
-        warnings.warn(
-            "CG terminated in {} iterations with average residual norm {}"
-            " which is larger than the tolerance of {} specified by"
-            " linear_operator.settings.cg_tolerance."
-            " If performance is affected, consider raising the maximum number of CG iterations by running code in"
-            " a linear_operator.settings.max_cg_iterations(value) context.".format(
-                k_done, residual_norm.mean(), tolerance
-            ),
-            UserWarning,
-        )
+        _warn_tolerance_missed(k_done, residual_norm.mean(), tolerance)
 
     record_solve(solver="linear_cg", iterations=int(k_done), tolerance_reached=bool(tolerance_reached) or n_iter == 0,
                  residual_norm=residual_norm.detach().reshape(-1).clone(), tolerance=float(tolerance))
@@ -191,6 +182,19 @@ def linear_cg(
         t_mat = t_mat[: last + 1, : last + 1]
         return result, t_mat.permute(-1, 0, 1).contiguous()       # (reference :426-427)
     return result
+
+
+def _warn_tolerance_missed(k_done, mean_residual_norm, tolerance) -> None:
+    """The reference's warning for a run that ends at the iteration cap (:411-421)."""
+    warnings.warn(
+        "CG terminated in {} iterations with average residual norm {}"
+        " which is larger than the tolerance of {} specified by"
+        " linear_operator.settings.cg_tolerance."
+        " If performance is affected, consider raising the maximum number of CG iterations by running code in"
+        " a linear_operator.settings.max_cg_iterations(value) context.".format(k_done, mean_residual_norm, tolerance),
+        UserWarning,
+        stacklevel=2,      # (attributed to the solver that calls this, as before it was a helper)
+    )
 
 
 def last_solve_info():
@@ -337,6 +341,42 @@ def _two_launch_loop(op, rhs_is_zero, x, r, has_converged, n_iter, max_iter, tol
     k_done = int(flags[2].item())
     rnorm = scal[4 * p : 5 * p].unsqueeze(0)
     return x, rnorm, k_done, done, hist
+
+
+_HISTORY_EPS = 1e-30           # the division guard of `_cg_with_history` (see there)
+
+
+def _cg_with_history(op, rhs: torch.Tensor, n_hist: int, tolerance: float, max_iter: int, stop_after: float = 1e-10):
+    """One CG run from x = 0 on the columns `rhs` (n, p <= 256 on the GPU) that keeps every column's coefficients: the internal entry
+    of `sparse_logdet`.  Returns (x, hist [n_hist][2][p] of (alpha, beta), iterations, residual norms (p,) of the NORMALISED
+    columns, tolerance reached, column norms (p,), whether the fused loop ran); x is scaled back to `rhs`.  Columns are normalised and the first
+    min(n_hist, max_iter - 1) iterations cannot stop the run, as `linear_cg` does it for `n_tridiag`; what `linear_cg` returns is
+    not touched.  The fused two-launch loop records the history on the device; where it declines (a width it does not take, more
+    than 1024 partial rows, `TWO_LAUNCH` off, CPU operands) the recurrences run as tensor ops around the same operator
+    (`_cpu.cg_history_loop`), with the same guards.  The division guard is 1e-30 and not linear_cg's 1e-10: with the latter a
+    column's beta is zeroed — its tridiagonal matrix cut — once |r|² < 1e-10, a residual of 1e-5, which would cap the quadrature's
+    accuracy at 1e-10 per column; `stop_after` (|r| < 1e-10) still freezes a column, and that row ends its matrix."""
+    from .. import _cpu
+
+    n, p = rhs.shape
+    norm = _be.coldot(rhs, rhs).sqrt_()
+    is_zero = norm.lt(_HISTORY_EPS)
+    norm = norm.masked_fill(is_zero, 1)
+    r = rhs.div(norm.unsqueeze(0)).contiguous()
+    n_hist = max(1, min(int(n_hist), max_iter))
+    two = None
+    if r.is_cuda and TWO_LAUNCH and p <= 256 and isinstance(op, SparseOperator) and op.dtype == r.dtype:
+        x = torch.zeros_like(r)
+        has_converged = _colnorm(r).lt(stop_after)
+        two = _two_launch_loop(op, is_zero.unsqueeze(0), x, r.clone(), has_converged, max_iter, max_iter, tolerance, _HISTORY_EPS,
+                               stop_after, n_hist=n_hist, min_iter_floor=min(n_hist, max_iter - 1))
+    if two is not None:
+        x, rnorm, k_done, done, hist = two
+        rnorm = rnorm.reshape(-1)
+    else:
+        x, hist, k_done, rnorm, done = _cpu.cg_history_loop(lambda v: checked(op(v), r.dtype), _be.coldot, r, n_hist, tolerance,
+                                                            max_iter, _HISTORY_EPS, stop_after)
+    return x.mul(norm.unsqueeze(0)), hist, int(k_done), rnorm, bool(done), norm, two is not None
 
 
 def _tridiag_from_history(hist: torch.Tensor, n_tridiag: int, rows: int, t_mat: torch.Tensor) -> int:
