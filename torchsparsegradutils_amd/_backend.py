@@ -324,6 +324,19 @@ SIGNATURES_QUADRATURE = {
 # against the header)
 STAGED_QUADRATURE = {"tsgu_hip_quadrature.h": SIGNATURES_QUADRATURE}
 
+# the additive entries of csrc/tsgu_hip_ciq.h (same library, same ABI version): the sixth STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI` and the five registries above)
+SIGNATURES_CIQ = {
+    "tsgu_ciq_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                 ctypes.POINTER(_i64)]),
+    "tsgu_ciq_update": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_ciq_stop": (_int, [_int, _i64, _int, _ptr, _dbl, _ptr, _ptr, _ptr, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_sqrt_cpu.py holds it against
+# the header)
+STAGED_CIQ = {"tsgu_hip_ciq.h": SIGNATURES_CIQ}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -347,7 +360,7 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
-                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values()):
+                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -2156,3 +2169,31 @@ def rademacher_fill(n: int, p: int, seed: int, dtype: torch.dtype, device) -> to
     out = torch.empty((n, p), dtype=dtype, device=device)
     launch("tsgu_rademacher_fill", device, vtype_of(out), n, p, _i64(int(seed)).value, out)
     return out
+
+
+# ---- contour-quadrature update (csrc/tsgu_hip_ciq.h; sparse_sqrt.py) ---------------------------------------------------------------
+def ciq_geometry(dtype: torch.dtype, n: int, p: int):
+    """(shift cap, plane alignment in elements, rows per workgroup, workgroups) of tsgu_ciq_update for an (n, p) block.  Host only;
+    a width the lane geometry does not cover raises with the rule."""
+    fn = load_library().tsgu_ciq_geometry
+    cap, align, rows, groups = _int(0), _int(0), _i64(0), _i64(0)
+    rc = fn(_VTYPE[dtype], n, p, ctypes.byref(cap), ctypes.byref(align), ctypes.byref(rows), ctypes.byref(groups))
+    if rc == -3:
+        raise RuntimeError(f"tsgu_ciq_geometry: {p} simultaneous right-hand sides are not supported by the fused kernels, which take "
+                           f"{krylov_width_rule(dtype)}")
+    check(rc, "tsgu_ciq_geometry")
+    return cap.value, align.value, rows.value, groups.value
+
+
+def ciq_update(zc, zp, wpp, wp, shift_stride: int, acc, keep, scal, omega, done, flags) -> None:
+    """One tsgu_ciq_update launch on the (n, p) state `zc`: see csrc/tsgu_hip_ciq.h.  `keep` may be None."""
+    dev = require_device(zc, zp, wpp, wp, acc, keep, scal, omega, done, flags)
+    n, p = zc.shape
+    launch("tsgu_ciq_update", dev, vtype_of(zc), n, p, omega.numel(), zc, zp, wpp, wp, int(shift_stride), acc, keep, scal, omega, done,
+           flags)
+
+
+def ciq_stop(scal, tol: float, est, done, flags) -> None:
+    """One tsgu_ciq_stop launch on scal [S][12][p]: see csrc/tsgu_hip_ciq.h."""
+    dev = require_device(scal, est, done, flags)
+    launch("tsgu_ciq_stop", dev, vtype_of(scal), scal.size(2), scal.size(0), scal, float(tol), est, done, flags)

@@ -870,3 +870,25 @@ def tridiag_quadrature(coef: torch.Tensor, kind: int = 0, fn: int = 0, scale=Non
     if scale is not None:
         out = out * scale.to(torch.float64)
     return out.to(coef.dtype), info
+
+
+# ---- contour quadrature (sparse_sqrt.py): the composition the fused loop of csrc/ciq_impl.h replaces ---------------------------------
+
+def ciq_apply(A: torch.Tensor, B: torch.Tensor, sigma: torch.Tensor, omega: torch.Tensor, tolerance: float, max_iter: int, want_keep: bool):
+    """Σ_q ω_q (A + σ_q I)⁻¹ B for the dense (n, p) block B: the unfused multi-shift `minres(A, B, shifts=σ)` and the weighted sum.
+    Returns (result, keep, est): `keep` [n][S][p] holds the S solutions as an SDDMM operand (None unless `want_keep`), `est` (p,)
+    each column's largest TRUE relative residual over the shifts (the unfused solver keeps no estimates; a zero column reports 0)."""
+    from .utils._operator import SparseOperator
+    from .utils.minres import MINRESSettings, minres
+
+    _cpu_only(B, sigma, omega)
+    n, p = B.shape
+    S = sigma.numel()
+    sols = minres(A, B, shifts=sigma, max_iter=int(max_iter),
+                  settings=MINRESSettings(max_cg_iterations=int(max_iter), minres_tolerance=float(tolerance))).reshape(S, n, p)
+    out = torch.einsum("q,qnc->nc", omega, sols)
+    keep = sols.permute(1, 0, 2).contiguous()
+    resid = SparseOperator(A)(keep.reshape(n, S * p)).reshape(n, S, p) + sigma.reshape(1, S, 1) * keep - B.unsqueeze(1)
+    bnorm = torch.linalg.vector_norm(B, dim=0)
+    est = torch.linalg.vector_norm(resid, dim=0).amax(dim=0) / torch.where(bnorm > 0, bnorm, torch.ones_like(bnorm))
+    return out, (keep if want_keep else None), est
