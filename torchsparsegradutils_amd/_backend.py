@@ -337,6 +337,19 @@ SIGNATURES_CIQ = {
 # the header)
 STAGED_CIQ = {"tsgu_hip_ciq.h": SIGNATURES_CIQ}
 
+# the additive entries of csrc/tsgu_hip_expm.h (same library, same ABI version): the seventh STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI` and the six registries above)
+SIGNATURES_EXPM = {
+    "tsgu_expm_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "tsgu_cheb_step": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _dbl, _ptr, _int, _int, _ptr, _int, _int, _ptr, _int, _ptr]),
+    "tsgu_cheb_combine": (_int, [_int, _int, _int, _i64, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _ptr, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_expm_cpu.py holds it against
+# the header)
+STAGED_EXPM = {"tsgu_hip_expm.h": SIGNATURES_EXPM}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -360,7 +373,7 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
-                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values()):
+                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -2197,3 +2210,35 @@ def ciq_stop(scal, tol: float, est, done, flags) -> None:
     """One tsgu_ciq_stop launch on scal [S][12][p]: see csrc/tsgu_hip_ciq.h."""
     dev = require_device(scal, est, done, flags)
     launch("tsgu_ciq_stop", dev, vtype_of(scal), scal.size(2), scal.size(0), scal, float(tol), est, done, flags)
+
+
+# ---- Chebyshev recurrence (csrc/tsgu_hip_expm.h; sparse_expm.py) --------------------------------------------------------------------
+def expm_geometry(dtype: torch.dtype, n: int, p: int):
+    """(time cap, chunk cap, plane alignment in elements, rows per workgroup, workgroups) of tsgu_cheb_step / tsgu_cheb_combine for an
+    (n, p) block.  Host only; a width the lane geometry does not cover raises with the rule."""
+    fn = load_library().tsgu_expm_geometry
+    tcap, ccap, align, rows, groups = _int(0), _int(0), _int(0), _i64(0), _i64(0)
+    rc = fn(_VTYPE[dtype], n, p, ctypes.byref(tcap), ctypes.byref(ccap), ctypes.byref(align), ctypes.byref(rows), ctypes.byref(groups))
+    if rc == -3:
+        raise RuntimeError(f"tsgu_expm_geometry: {p} simultaneous right-hand sides are not supported by the fused kernels, which take "
+                           f"{krylov_width_rule(dtype)}")
+    check(rc, "tsgu_expm_geometry")
+    return tcap.value, ccap.value, align.value, rows.value, groups.value
+
+
+def cheb_step(prod, x, prev, alpha: float, beta: float, gamma: float, flags, src=None, src_slot: int = 0, chunk=None, slot: int = 0) -> None:
+    """One tsgu_cheb_step launch on the (n, p) state `prev`: see csrc/tsgu_hip_expm.h.  `prod`, `src` and `chunk` may be None; `src`
+    and `chunk` are (n, slots, p)."""
+    dev = require_device(prod, x, prev, src, chunk, flags)
+    n, p = prev.shape
+    launch("tsgu_cheb_step", dev, vtype_of(prev), n, p, prod, x, prev, float(alpha), float(beta), float(gamma), src,
+           0 if src is None else src.size(1), int(src_slot), chunk, 0 if chunk is None else chunk.size(1), int(slot), flags)
+
+
+def cheb_combine(mode: int, chunk, coef, planes, plane_stride: int, flags, accumulate: bool = False) -> None:
+    """One tsgu_cheb_combine launch: `chunk` (n, m, p), `coef` (m, T, p), `planes` the T arrays (n, p) `plane_stride` elements apart
+    (mode 0 writes them, mode 1 reads them): see csrc/tsgu_hip_expm.h."""
+    dev = require_device(chunk, coef, planes, flags)
+    n, m, p = chunk.shape
+    launch("tsgu_cheb_combine", dev, vtype_of(chunk), int(mode), int(bool(accumulate)), n, p, m, coef.size(1), chunk, coef, planes,
+           int(plane_stride), flags)

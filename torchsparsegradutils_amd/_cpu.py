@@ -892,3 +892,49 @@ def ciq_apply(A: torch.Tensor, B: torch.Tensor, sigma: torch.Tensor, omega: torc
     bnorm = torch.linalg.vector_norm(B, dim=0)
     est = torch.linalg.vector_norm(resid, dim=0).amax(dim=0) / torch.where(bnorm > 0, bnorm, torch.ones_like(bnorm))
     return out, (keep if want_keep else None), est
+
+
+# ---- Chebyshev expansion of exp(t A) B (sparse_expm.py): the composition the fused loop of csrc/expm_impl.h replaces --------------------
+
+def expm_apply(matmul, B: torch.Tensor, coef: torch.Tensor, a: float, b: float, want_keep: bool):
+    """Σ_k coef[k] ∘ w_k for the dense (n, p) block B with w_0 = B, w_1 = Â w_0, w_{k+1} = 2 Â w_k − w_{k−1}, Â = a·A + b·I, in torch
+    ops around the closure `matmul` (v -> A v): CPU operands, and the baseline tools/expmbench.py times on the GPU.  `coef` is the
+    (K + 1, T, p) table of sparse_expm._coefficients in B's dtype.  Returns (Y (T, n, p), [w_0 ... w_K] or None)."""
+    K = coef.size(0) - 1
+    w_prev, w = None, B
+    Y = coef[0].unsqueeze(1) * w.unsqueeze(0)
+    W = [w] if want_keep else None
+    for k in range(K):
+        f = 1.0 if k == 0 else 2.0
+        nxt = torch.add(matmul(w).mul_(f * a), w, alpha=f * b)
+        if w_prev is not None:
+            nxt.sub_(w_prev)
+        w_prev, w = w, nxt
+        Y.addcmul_(coef[k + 1].unsqueeze(1), w.unsqueeze(0))
+        if want_keep:
+            W.append(w)
+    return Y, W
+
+
+def expm_adjoint(matmul, sddmm, G: torch.Tensor, coef: torch.Tensor, a: float, b: float, W, need_b: bool = True):
+    """The adjoint of :func:`expm_apply` for G (T, n, p): μ_k = Σ_j coef[k, j] ∘ G_j + f_k Â μ_{k+1} − μ_{k+2} for k = K ... 0 with
+    f_0 = 1, f_k = 2.  Returns (a Σ_{k<K} f_k sddmm(μ_{k+1}, w_k) or None without `W`, μ_0 or None): `sddmm(L, R)` gives
+    Σ_c L[i, c] R[j, c] at the stored entries (i, j)."""
+    K = coef.size(0) - 1
+    mu1 = mu2 = None                                              # μ_{k+1}, μ_{k+2}; None stands for zero
+    gvals = None
+    for k in range(K, -1, -1):
+        if k == 0 and not need_b:
+            break
+        f = 1.0 if k == 0 else 2.0
+        mu = (coef[k].unsqueeze(1) * G).sum(dim=0)
+        if mu1 is not None:
+            mu.add_(matmul(mu1), alpha=f * a).add_(mu1, alpha=f * b)
+        if mu2 is not None:
+            mu.sub_(mu2)
+        mu2, mu1 = mu1, mu
+        if W is not None and k >= 1:                              # μ_k pairs with w_{k−1}, weighted f_{k−1}·a
+            part = sddmm(mu1, W[k - 1])
+            fk = a if k == 1 else 2.0 * a
+            gvals = part.mul_(fk) if gvals is None else gvals.add_(part, alpha=fk)
+    return gvals, (mu1 if need_b else None)

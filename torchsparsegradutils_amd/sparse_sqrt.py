@@ -100,7 +100,8 @@ def _ciq_rule(lo: float, hi: float, num_quad: int):
 
 # ---- checks ------------------------------------------------------------------------------------------------------------------------
 
-def _check(who: str, A, B, num_quad, bounds, tolerance, max_iter, lanczos_steps):
+def _check_operands(who: str, A, B) -> None:
+    """The checks every matrix function of a sparse symmetric A applied to a dense block B shares (sparse_expm.py uses them too)."""
     if not isinstance(A, torch.Tensor):
         raise ValueError(f"{who}: A should be an instance of torch.Tensor")
     if A.layout not in (torch.sparse_coo, torch.sparse_csr):
@@ -122,6 +123,10 @@ def _check(who: str, A, B, num_quad, bounds, tolerance, max_iter, lanczos_steps)
         raise ValueError(f"{who}: B must have A's dtype, got {B.dtype} and {A.dtype}")
     if B.device != A.device:
         raise RuntimeError(f"{who}: B must be on the device of A, got {B.device} and {A.device}")
+
+
+def _check(who: str, A, B, num_quad, bounds, tolerance, max_iter, lanczos_steps):
+    _check_operands(who, A, B)
     if not 1 <= int(num_quad) <= _MAX_QUAD:
         raise ValueError(f"{who}: num_quad must lie in [1, {_MAX_QUAD}], got {num_quad}")
     if int(max_iter) < 1:
