@@ -4,7 +4,8 @@ Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_tria
 ``sparse_generic_lstsq`` / ``sparse_logsumexp`` / ``sparse_bidir_logsumexp`` (reference ``torchsparsegradutils/__init__.py:1-16``),
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
 ``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
-``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` beside them;
+``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
+``sparse_topk_mm`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -29,6 +30,7 @@ from .sparse_softmax import SparseSoftmax, sparse_log_softmax, sparse_softmax
 from .sparse_spgemm import SparseSpGEMM, sparse_spgemm
 from .sparse_sqrt import SparseInvSqrtMM, sparse_inv_sqrt_mm, sparse_sqrt_mm
 from .sparse_expm import SparseExpmMM, sparse_expm_mm
+from .sparse_topk import SparseTopkMM, sparse_topk_mm
 from .sparse_solve import (
     SparseGenericSolve,
     SparseTriangularSolve,
@@ -66,6 +68,8 @@ __all__ = [
     "SparseInvSqrtMM",
     "sparse_expm_mm",
     "SparseExpmMM",
+    "sparse_topk_mm",
+    "SparseTopkMM",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",

@@ -350,6 +350,19 @@ SIGNATURES_EXPM = {
 # the header)
 STAGED_EXPM = {"tsgu_hip_expm.h": SIGNATURES_EXPM}
 
+# the additive entries of csrc/tsgu_hip_topk.h (same library, same ABI version): the eighth STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI` and the seven registries above)
+SIGNATURES_TOPK = {
+    "tsgu_topk_geometry": (_int, [_int, _i64, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_topk_mm": (_int, [_int, _ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _dbl, _int, _i64, _ptr, _ptr, _ptr, _int, _i64, _i64, _i64,
+                            _i64, _i64, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_topk_cpu.py holds it against
+# the header)
+STAGED_TOPK = {"tsgu_hip_topk.h": SIGNATURES_TOPK}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -373,7 +386,8 @@ def load_library():
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
-                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values()):
+                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
+                      *STAGED_TOPK.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -2242,3 +2256,23 @@ def cheb_combine(mode: int, chunk, coef, planes, plane_stride: int, flags, accum
     n, m, p = chunk.shape
     launch("tsgu_cheb_combine", dev, vtype_of(chunk), int(mode), int(bool(accumulate)), n, p, m, coef.size(1), chunk, coef, planes,
            int(plane_stride), flags)
+
+
+# ---- top-k of a dense product as CSR arrays (csrc/tsgu_hip_topk.h; sparse_topk.py) --------------------------------------------------
+TOPK_CAUSAL, TOPK_EXCLUDE_SELF = 1, 2
+
+
+def topk_geometry(dtype: torch.dtype, d: int = 1, k: int = 1):
+    """(cap on k, rows per workgroup, keys per tile, columns per LDS stage, dynamic LDS bytes) of tsgu_topk_mm.  Host only; a k above
+    the cap raises."""
+    return _query("tsgu_topk_geometry", _VTYPE[dtype], int(d), int(k))
+
+
+def topk_mm(Q, K, key_bias, k: int, scale: float, flags: int, causal_offset: int, crow, col, val) -> None:
+    """One tsgu_topk_mm launch: Q (b, n, d), K (b, m, d) and key_bias (b, m) or None, contiguous; crow (n + 1,) shared by the batch
+    items; col and val (b, nnz) are written.  See csrc/tsgu_hip_topk.h."""
+    dev = require_device(Q, K, key_bias, crow, col, val)
+    b, n, d = Q.shape
+    m = K.size(1)
+    launch("tsgu_topk_mm", dev, vtype_of(Q), Q, K, key_bias, n, m, d, int(k), float(scale), int(flags), int(causal_offset), crow, col, val,
+           itype_of(crow), b, n * d, m * d, m, col.size(1))

@@ -938,3 +938,37 @@ def expm_adjoint(matmul, sddmm, G: torch.Tensor, coef: torch.Tensor, a: float, b
             fk = a if k == 1 else 2.0 * a
             gvals = part.mul_(fk) if gvals is None else gvals.add_(part, alpha=fk)
     return gvals, (mu1 if need_b else None)
+
+
+# ---- the k largest of a dense product per row (sparse_topk.py): the composition the fused kernel of csrc/topk_impl.h replaces -----------
+
+def topk_mm(Q: torch.Tensor, K: torch.Tensor, bias, k: int, scale: float, causal: bool, exclude_self: bool, counts: torch.Tensor,
+            index_dtype):
+    """(col (b, nnz), val (b, nnz)) of the best `counts[i]` allowed scores of every row of scale·Q·Kᵀ + bias for Q (b, n, d), K (b, m, d)
+    and bias (b, m) or None: the dense product in float32 (float64 for float64), a stable descending sort (NaN first, the lower
+    column first among equal scores), the allowed columns moved to the front by a second stable sort, columns ascending at the end."""
+    _cpu_only(Q, K, bias)
+    b, n, _ = Q.shape
+    m = K.size(1)
+    acc = torch.float64 if Q.dtype == torch.float64 else torch.float32
+    S = torch.matmul(Q.to(acc), K.to(acc).transpose(1, 2))
+    if scale != 1.0:
+        S = S * scale
+    if bias is not None:
+        S = S + bias.to(acc).unsqueeze(1)
+    i = torch.arange(n).unsqueeze(1)
+    j = torch.arange(m).unsqueeze(0)
+    allowed = torch.ones((n, m), dtype=torch.bool)
+    if causal:
+        allowed &= j <= i + (m - n)
+    if exclude_self:
+        allowed &= j != i
+    order = torch.sort(S, dim=-1, descending=True, stable=True).indices
+    barred = (~allowed).expand(b, n, m).gather(2, order)
+    order = order.gather(2, torch.sort(barred.to(torch.uint8), dim=-1, stable=True).indices)
+    kk = min(k, m)
+    keep = torch.arange(kk).unsqueeze(0) < counts.unsqueeze(1)                 # (n, kk): a row's first counts[i] places
+    cols = torch.where(keep, order[:, :, :kk], torch.full((), m, dtype=torch.int64)).sort(dim=-1).values
+    vals = S.gather(2, cols.clamp(max=max(m - 1, 0))) if m else S[:, :, :0]
+    keep = keep.expand(b, n, kk)
+    return cols[keep].reshape(b, -1).to(index_dtype), vals[keep].reshape(b, -1).to(Q.dtype)

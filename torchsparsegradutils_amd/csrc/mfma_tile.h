@@ -1,5 +1,5 @@
 // The matrix-core tile layer: what the kernels that multiply on the MFMA units share (indexed_mm_impl.h, bsr_impl.h,
-// bsr_attention_impl.h).  Every product is C[m][n] = sum_k X[m][k] * Y[n][k] over two LDS images, each row with one 16-byte pad, on
+// bsr_attention_impl.h, topk_impl.h).  Every product is C[m][n] = sum_k X[m][k] * Y[n][k] over two LDS images, each row with one 16-byte pad, on
 // 16 x 16 tiles.  MFMA lane maps (cdna_hip_programming.md §3), lane l = (r, q) = (l & 15, l >> 4):
 //   f32  16x16x4f32:  lane l holds X[r][k0 + q] and Y[r][k0 + q];              C: col = r, row = 4 q + reg
 //   f64  16x16x4f64:  A/B as f32;                                             C: col = r, row = q + 4 reg
