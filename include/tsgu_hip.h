@@ -111,6 +111,21 @@ int tsgu_csr_spmm(int vtype, int itype,
 int64_t tsgu_spmm_num_blocks(int vtype, int64_t n_rows, int64_t nnz_per_item, int64_t p, int64_t max_row_nnz);
 
 /*
+ * Lane geometry of the plan-free kernels, answered on the host by the launchers' own rules (no device is touched; no reference
+ * counterpart).  kernel: 0 = K1 / K2 (CSR SpMM), 1 = K3 (CSR SDDMM), 2 = the COO flavour of K3, 3 = the fused backward K2+K3
+ * (n_rows = rows of the walked pattern: the columns of A).  wide_ok: every dense operand's base address, leading dimension and
+ * batch stride allows 16-byte lanes.  col_strided (kernel 0 only): B / C have a column stride other than 1.
+ * Out: vec elements per lane (1 or 16 bytes' worth), column_lanes x entry_lanes lanes per row (per entry for the COO flavour, where
+ * entry_lanes is 1), column_tiles tiles of vec * column_lanes columns, row_runs runs of 256 / (column_lanes * entry_lanes) rows per
+ * workgroup (kernel 0; 1 otherwise) and stage_entries, the stored entries a workgroup stages per pass.
+ * TSGU_ERR_BAD_DTYPE: unknown vtype, F64 with kernel 3.  TSGU_ERR_BAD_ARG: unknown kernel, a negative size, a NULL output, and for
+ * kernel 3 a width the launcher refuses (column_tiles != 1).
+ */
+int tsgu_csr_geometry(int kernel, int vtype, int64_t n_rows, int64_t nnz_per_item, int64_t p, int64_t max_row_nnz,
+                      int wide_ok, int col_strided,
+                      int* vec, int* column_lanes, int* entry_lanes, int64_t* column_tiles, int* row_runs, int* stage_entries);
+
+/*
  * K3  out[k] = alpha * < G[row(k), :], B[col(k), :] >   for every stored entry k of A
  * (sparsity-masked SDDMM; no row-index expansion, no nnz×p temporaries)
  * replaces: repeat_interleave + 2×index_select + mul + sum

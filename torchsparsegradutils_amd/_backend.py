@@ -54,6 +54,8 @@ SIGNATURES = {
          _ptr, _i64, _ptr, _int, _ptr],
     ),
     "tsgu_spmm_num_blocks": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "tsgu_csr_geometry": (_int, [_int, _int, _i64, _i64, _i64, _i64, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                 ctypes.POINTER(_int), ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "tsgu_csr_sddmm": (
         _int,
         [_int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i64, _ptr, _dbl, _int, _i64, _i64,
@@ -604,6 +606,17 @@ def fused_backward_supported(dtype: torch.dtype, p: int) -> bool:
         return False
     vec = wide if p % wide == 0 else 1
     return (p + vec - 1) // vec <= 64
+
+
+CSR_SPMM, CSR_SDDMM, COO_SDDMM, CSR_MM_BACKWARD = 0, 1, 2, 3
+
+
+def csr_geometry(kernel: int, dtype: torch.dtype, n_rows: int, nnz: int, p: int, max_row_nnz: int = 0, wide_ok: bool = True,
+                 col_strided: bool = False):
+    """(vec, column_lanes, entry_lanes, column_tiles, row_runs, stage_entries) of a plan-free kernel (`CSR_SPMM`, `CSR_SDDMM`,
+    `COO_SDDMM`, `CSR_MM_BACKWARD`) for these sizes, answered on the host by the launchers' own rules; raises where they refuse."""
+    return _query("tsgu_csr_geometry", int(kernel), _VTYPE[dtype], int(n_rows), int(nnz), int(p), int(max_row_nnz), int(bool(wide_ok)),
+                  int(bool(col_strided)))
 
 
 class _RowpackPlanStruct(ctypes.Structure):

@@ -1,5 +1,6 @@
 // extern "C" entry points for K1/K2/K3 (declared in include/tsgu_hip.h).
 // Argument validation lives here; the typed launchers are in spmm_*.hip / sddmm_*.hip.
+#include "bwd_impl.h"
 #include "sddmm_impl.h"
 #include "spmm_impl.h"
 
@@ -214,6 +215,62 @@ int64_t tsgu_spmm_num_blocks(int vtype, int64_t n_rows, int64_t nnz_per_item, in
     const int64_t rpb = kBlock / (g.cl * g.ep);
     const int64_t rows = rpb * spmm_row_mult(n_rows, nnz_per_item, rpb);
     return (n_rows + rows - 1) / rows;
+}
+
+int tsgu_csr_geometry(int kernel, int vtype, int64_t n_rows, int64_t nnz_per_item, int64_t p, int64_t max_row_nnz,
+                      int wide_ok, int col_strided,
+                      int* vec, int* column_lanes, int* entry_lanes, int64_t* column_tiles, int* row_runs, int* stage_entries) {
+    if (kernel < 0 || kernel > 3 || n_rows < 0 || nnz_per_item < 0 || p < 0 || max_row_nnz < 0) return TSGU_ERR_BAD_ARG;
+    if (!vec || !column_lanes || !entry_lanes || !column_tiles || !row_runs || !stage_entries) return TSGU_ERR_BAD_ARG;
+    // Parameter blocks as a caller's operands would fill them: leading dimensions of p, and base addresses (never read) that
+    // are 16-byte aligned or not.  The launchers' own helpers then decide.
+    const void* const base = reinterpret_cast<const void*>(static_cast<uintptr_t>(wide_ok ? 16 : 4));
+    RowGeom g{};
+    int runs = 1, cap = 0;
+    auto answer = [&](auto v) -> int {
+        using V = decltype(v);
+        if (kernel == 0) {
+            SpmmParams P{};
+            P.n_rows = n_rows, P.nnz_per_item = nnz_per_item, P.p = p, P.max_row_nnz = max_row_nnz;
+            P.B = base, P.C = const_cast<void*>(base), P.ldb = P.ldc = p;
+            P.b_cs = P.c_cs = col_strided ? 2 : 1;
+            g = spmm_geom<V>(P, 1);
+            runs = spmm_row_mult(n_rows, nnz_per_item, spmm_rows_per_block(g));
+            cap = kStageCap;
+        } else if (kernel == 1) {
+            SddmmParams P{};
+            P.n_rows = n_rows, P.nnz_per_item = nnz_per_item, P.p = p;
+            P.R = P.Cm = base, P.ldr = P.ldc = p;
+            g = sddmm_geom<V>(P, 1);
+            cap = kSddmmCap;
+        } else if (kernel == 2) {
+            CooSddmmParams P{};
+            P.nnz = nnz_per_item, P.p = p;
+            P.R = P.Cm = base, P.ldr = P.ldc = p;
+            g = coo_sddmm_geom<V>(P);
+            cap = kSddmmCap;
+        } else {
+            if constexpr (sizeof(V) <= 4) {
+                BwdParams P{};
+                P.n_rows_t = n_rows, P.nnz_per_item = nnz_per_item, P.p = p;
+                P.G = P.B = base, P.gradB = const_cast<void*>(base), P.ldg = P.ldb = P.ldo = p;
+                g = bwd_geom<V>(P, 1);
+                if (g.col_tiles != 1) return TSGU_ERR_BAD_ARG;  // as bwd_launch
+                cap = kBwdCap;
+            } else {
+                return TSGU_ERR_BAD_DTYPE;
+            }
+        }
+        return TSGU_OK;
+    };
+    if (const int rc = with_value_type<float, double, bf16_t>(vtype, answer)) return rc;
+    *vec = g.vec;
+    *column_lanes = g.cl;
+    *entry_lanes = g.ep;
+    *column_tiles = g.col_tiles;
+    *row_runs = runs;
+    *stage_entries = cap;
+    return TSGU_OK;
 }
 
 int tsgu_csr_spmm(int vtype, int itype, int64_t n_rows, int64_t n_cols, int64_t nnz_per_item,

@@ -199,13 +199,20 @@ __global__ __launch_bounds__(kBlock) void csr_mm_backward_kernel(const BwdParams
     }
 }
 
-template <typename V, typename I>
-int bwd_launch(BwdParams P, int64_t batch, hipStream_t stream) {
+// The lane geometry of a launch (also what tsgu_csr_geometry reports).
+template <typename V>
+inline RowGeom bwd_geom(const BwdParams& P, int64_t batch) {
     constexpr int wide = VT<V>::kWide;
     bool can = (P.p % wide == 0) && (P.ldg % wide == 0) && (P.ldb % wide == 0) && (P.ldo % wide == 0) &&
                aligned16(P.G) && aligned16(P.B) && aligned16(P.gradB);
     if (batch > 1) can = can && (P.g_bs % wide == 0) && (P.b_bs % wide == 0) && (P.o_bs % wide == 0);
-    const RowGeom g = pick_geom(wide, can, P.p);
+    return pick_geom(wide, can, P.p);
+}
+
+template <typename V, typename I>
+int bwd_launch(BwdParams P, int64_t batch, hipStream_t stream) {
+    constexpr int wide = VT<V>::kWide;
+    const RowGeom g = bwd_geom<V>(P, batch);
     if (g.col_tiles != 1) return TSGU_ERR_BAD_ARG;  // p > CL·VEC: caller uses K2 + K3
     const int64_t rpb = kBlock / (g.cl * g.ep);
     P.nblocks = (P.n_rows_t + rpb - 1) / rpb;

@@ -216,12 +216,29 @@ __global__ __launch_bounds__(kBlock) void coo_sddmm_kernel(const CooSddmmParams 
     }
 }
 
-template <typename V, typename I>
-int sddmm_launch(SddmmParams P, int64_t batch, hipStream_t stream) {
+// The lane geometry of a launch (also what tsgu_csr_geometry reports).
+template <typename V>
+inline RowGeom sddmm_geom(const SddmmParams& P, int64_t batch) {
     constexpr int wide = VT<V>::kWide;
     bool can = (P.p % wide == 0) && (P.ldr % wide == 0) && (P.ldc % wide == 0) && aligned16(P.R) && aligned16(P.Cm);
     if (batch > 1) can = can && (P.r_bs % wide == 0) && (P.c_bs % wide == 0);
-    const RowGeom g = pick_geom(wide, can, P.p);
+    return pick_geom(wide, can, P.p);
+}
+
+// COO: a group of CL lanes per entry, no entry lanes
+template <typename V>
+inline RowGeom coo_sddmm_geom(const CooSddmmParams& P) {
+    constexpr int wide = VT<V>::kWide;
+    const bool can = (P.p % wide == 0) && (P.ldr % wide == 0) && (P.ldc % wide == 0) && aligned16(P.R) && aligned16(P.Cm);
+    RowGeom g = pick_geom(wide, can, P.p);
+    g.ep = 1;
+    return g;
+}
+
+template <typename V, typename I>
+int sddmm_launch(SddmmParams P, int64_t batch, hipStream_t stream) {
+    constexpr int wide = VT<V>::kWide;
+    const RowGeom g = sddmm_geom<V>(P, batch);
     const int64_t rpb = kBlock / (g.cl * g.ep);
     P.nblocks = (P.n_rows + rpb - 1) / rpb;
     P.col_tiles = g.col_tiles;
@@ -240,8 +257,7 @@ int sddmm_launch(SddmmParams P, int64_t batch, hipStream_t stream) {
 template <typename V, typename I>
 int coo_sddmm_launch(CooSddmmParams P, hipStream_t stream) {
     constexpr int wide = VT<V>::kWide;
-    const bool can = (P.p % wide == 0) && (P.ldr % wide == 0) && (P.ldc % wide == 0) && aligned16(P.R) && aligned16(P.Cm);
-    const RowGeom g = pick_geom(wide, can, P.p);
+    const RowGeom g = coo_sddmm_geom<V>(P);
     P.col_tiles = g.col_tiles;
     const int64_t epb = kBlock / g.cl;
     int64_t nb = (P.nnz + epb - 1) / epb;
