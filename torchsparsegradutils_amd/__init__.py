@@ -5,7 +5,7 @@ Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_tria
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
 ``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
 ``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
-``sparse_topk_mm`` beside them;
+``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -31,6 +31,12 @@ from .sparse_spgemm import SparseSpGEMM, sparse_spgemm
 from .sparse_sqrt import SparseInvSqrtMM, sparse_inv_sqrt_mm, sparse_sqrt_mm
 from .sparse_expm import SparseExpmMM, sparse_expm_mm
 from .sparse_topk import SparseTopkMM, sparse_topk_mm
+from .sparse_semi_structured import (
+    SemiStructured,
+    sparse_semi_structured_linear,
+    sparse_semi_structured_mm,
+    sparse_semi_structured_prune,
+)
 from .sparse_solve import (
     SparseGenericSolve,
     SparseTriangularSolve,
@@ -70,6 +76,10 @@ __all__ = [
     "SparseExpmMM",
     "sparse_topk_mm",
     "SparseTopkMM",
+    "SemiStructured",
+    "sparse_semi_structured_prune",
+    "sparse_semi_structured_mm",
+    "sparse_semi_structured_linear",
     "gather_mm",
     "segment_mm",
     "sparse_triangular_solve",

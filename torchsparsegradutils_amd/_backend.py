@@ -365,6 +365,22 @@ SIGNATURES_TOPK = {
 # the header)
 STAGED_TOPK = {"tsgu_hip_topk.h": SIGNATURES_TOPK}
 
+# the additive entries of csrc/tsgu_hip_semi.h (same library, same ABI version): the ninth STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI` and the eight registries above)
+SIGNATURES_SEMI = {
+    "tsgu_semi_geometry": (_int, [_int, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_int)]),
+    "tsgu_semi_prune": (_int, [_int, _ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _int, _ptr]),
+    "tsgu_semi_expand": (_int, [_int, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _int, _ptr]),
+    "tsgu_semi_mm": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _ptr]),
+    "tsgu_semi_mm_t": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr]),
+    "tsgu_semi_sddmm": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_semi_structured_cpu.py holds
+# it against the header)
+STAGED_SEMI = {"tsgu_hip_semi.h": SIGNATURES_SEMI}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -389,7 +405,7 @@ def load_library():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
-                      *STAGED_TOPK.values()):
+                      *STAGED_TOPK.values(), *STAGED_SEMI.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -2289,3 +2305,77 @@ def topk_mm(Q, K, key_bias, k: int, scale: float, flags: int, causal_offset: int
     m = K.size(1)
     launch("tsgu_topk_mm", dev, vtype_of(Q), Q, K, key_bias, n, m, d, int(k), float(scale), int(flags), int(causal_offset), crow, col, val,
            itype_of(crow), b, n * d, m * d, m, col.size(1))
+
+
+# ---- 2:4 semi-structured operands (csrc/tsgu_hip_semi.h; sparse_semi_structured.py) --------------------------------------------------
+# Every wrapper takes 2-D tensors with unit stride in the last dimension (`rowmajor`) and passes the row strides on: sliced views
+# are consumed in place.  `meta` is the int32 (m, 4·ceil(k / 128)) position tensor of the header.
+SEMI_DENSE_T, SEMI_OUT_T = 1, 2
+
+
+def semi_geometry(dtype: torch.dtype, k: int = 0):
+    """(meta words per row, tile rows, tile columns, dense columns per LDS stage, 1 if the sparse instruction serves the dtype) of
+    tsgu_semi_mm.  Host only."""
+    return _query("tsgu_semi_geometry", _VTYPE[dtype], int(k))
+
+
+def semi_meta_words(k: int) -> int:
+    return 4 * ((k + 127) // 128)
+
+
+def semi_prune(W: torch.Tensor):
+    """(values (m, k / 2), meta) of the dense (m, k) matrix W: one tsgu_semi_prune launch."""
+    dev = require_device(W)
+    W = rowmajor(W)
+    m, k = W.shape
+    val = torch.empty((m, k // 2), dtype=W.dtype, device=dev)
+    meta = torch.empty((m, semi_meta_words(k)), dtype=torch.int32, device=dev)
+    launch("tsgu_semi_prune", dev, vtype_of(W), W, _ld(W), m, k, val, max(k // 2, 1), meta, max(meta.size(1), 4))
+    return val, meta
+
+
+def semi_expand(val: torch.Tensor, meta: torch.Tensor, k: int) -> torch.Tensor:
+    """The dense (m, k) matrix of (val, meta): one tsgu_semi_expand launch."""
+    dev = require_device(val, meta)
+    val = rowmajor(val)
+    m = val.size(0)
+    out = torch.empty((m, k), dtype=val.dtype, device=dev)
+    launch("tsgu_semi_expand", dev, vtype_of(val), val, _ld(val), meta, max(meta.size(1), 4), m, k, out, max(k, 1))
+    return out
+
+
+def semi_mm(val, meta, k: int, Y, bias, linear: bool, smfmac: bool) -> torch.Tensor:
+    """A·Y for Y (k, p) -> (m, p), or with `linear` Y·Aᵀ (+ bias) for Y (p, k) -> (p, m): one tsgu_semi_mm launch.  `smfmac` selects
+    the sparse matrix instruction (bfloat16 only)."""
+    dev = require_device(val, meta, Y, bias)
+    val, Y = rowmajor(val), rowmajor(Y)
+    m = val.size(0)
+    p = Y.size(0) if linear else Y.size(1)
+    out = torch.empty((p, m) if linear else (m, p), dtype=val.dtype, device=dev)
+    launch("tsgu_semi_mm", dev, vtype_of(val), val, _ld(val), meta, max(meta.size(1), 4), Y, _ld(Y), bias, out, max(out.size(1), 1), m, k, p,
+           SEMI_OUT_T if linear else SEMI_DENSE_T, int(bool(smfmac) and val.dtype == torch.bfloat16))
+    return out
+
+
+def semi_mm_t(val, meta, k: int, G, linear: bool) -> torch.Tensor:
+    """Aᵀ·G for G (m, p) -> (k, p), or with `linear` G·A for G (p, m) -> (p, k): one tsgu_semi_mm_t launch."""
+    dev = require_device(val, meta, G)
+    val, G = rowmajor(val), rowmajor(G)
+    m = val.size(0)
+    p = G.size(0) if linear else G.size(1)
+    out = torch.empty((p, k) if linear else (k, p), dtype=val.dtype, device=dev)
+    launch("tsgu_semi_mm_t", dev, vtype_of(val), val, _ld(val), meta, max(meta.size(1), 4), G, _ld(G), out, max(out.size(1), 1), m, k, p,
+           (SEMI_DENSE_T | SEMI_OUT_T) if linear else 0)
+    return out
+
+
+def semi_sddmm(meta, m: int, k: int, G, Y, linear: bool) -> torch.Tensor:
+    """The gradient of the kept values, (m, k / 2): G (m, p) against Y (k, p), or with `linear` G (p, m) against Y (p, k): one
+    tsgu_semi_sddmm launch."""
+    dev = require_device(meta, G, Y)
+    G, Y = rowmajor(G), rowmajor(Y)
+    p = G.size(0) if linear else G.size(1)
+    out = torch.empty((m, k // 2), dtype=G.dtype, device=dev)
+    launch("tsgu_semi_sddmm", dev, vtype_of(G), G, _ld(G), Y, _ld(Y), meta, max(meta.size(1), 4), out, max(k // 2, 1), m, k, p,
+           SEMI_DENSE_T if linear else 0)
+    return out

@@ -972,3 +972,54 @@ def topk_mm(Q: torch.Tensor, K: torch.Tensor, bias, k: int, scale: float, causal
     vals = S.gather(2, cols.clamp(max=max(m - 1, 0))) if m else S[:, :, :0]
     keep = keep.expand(b, n, kk)
     return cols[keep].reshape(b, -1).to(index_dtype), vals[keep].reshape(b, -1).to(Q.dtype)
+
+
+# ---- 2:4 semi-structured operands (sparse_semi_structured.py): what the kernels of csrc/semi_impl.h compute, in torch ops ---------------
+
+def semi_prune(W: torch.Tensor):
+    """(values (m, k / 2), positions (m, k / 4, 2) int64, ascending) of the dense (m, k) matrix W: per aligned group of four the two
+    entries that rank first by (|w| descending, column ascending).  A stable descending sort of |w|: torch sorts NaN above inf, and
+    -0 equals +0 once the sign is gone."""
+    _cpu_only(W)
+    m, k = W.shape
+    groups = W.reshape(m, k // 4, 4)
+    order = torch.sort(groups.abs(), dim=-1, descending=True, stable=True).indices
+    pos = order[..., :2].sort(dim=-1).values
+    return groups.gather(-1, pos).reshape(m, k // 2), pos
+
+
+def semi_dense(values: torch.Tensor, cols: torch.Tensor, k: int, dtype=None) -> torch.Tensor:
+    """The dense (m, k) matrix with `values` at the columns `cols` (both (m, k / 2)), +0 elsewhere."""
+    _cpu_only(values, cols)
+    out = torch.zeros((values.size(0), k), dtype=dtype or values.dtype)
+    return out.scatter_(1, cols, values.to(out.dtype))
+
+
+def semi_mm(values: torch.Tensor, cols: torch.Tensor, k: int, Y: torch.Tensor, bias, linear: bool) -> torch.Tensor:
+    """A·Y for Y (k, p), or with `linear` Y·Aᵀ (+ bias) for Y (p, k): accumulated in float32 for float32 and bfloat16 (float64 for
+    float64), rounded once."""
+    _cpu_only(values, cols, Y, bias)
+    acc = _bsr_acc(values.dtype)
+    A = semi_dense(values, cols, k, acc)
+    if not linear:
+        return (A @ Y.to(acc)).to(values.dtype)
+    out = Y.to(acc) @ A.t()
+    if bias is not None:
+        out = out + bias.to(acc)
+    return out.to(values.dtype)
+
+
+def semi_mm_backward(values, cols, k: int, Y, G, linear: bool, need_values: bool, need_dense: bool):
+    """(gradient of the kept values or None, gradient of the dense operand or None) of :func:`semi_mm`: the dense product G·Yᵀ read at
+    the kept columns, and Aᵀ·G."""
+    _cpu_only(values, cols, Y, G)
+    acc = _bsr_acc(values.dtype)
+    Ga, Ya = G.to(acc), Y.to(acc)
+    dvalues = ddense = None
+    if need_values:
+        full = Ga.t() @ Ya if linear else Ga @ Ya.t()                   # (m, k)
+        dvalues = full.gather(1, cols).to(values.dtype)
+    if need_dense:
+        A = semi_dense(values, cols, k, acc)
+        ddense = (Ga @ A if linear else A.t() @ Ga).to(values.dtype)
+    return dvalues, ddense

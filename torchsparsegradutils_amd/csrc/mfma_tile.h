@@ -1,10 +1,17 @@
 // The matrix-core tile layer: what the kernels that multiply on the MFMA units share (indexed_mm_impl.h, bsr_impl.h,
-// bsr_attention_impl.h, topk_impl.h).  Every product is C[m][n] = sum_k X[m][k] * Y[n][k] over two LDS images, each row with one 16-byte pad, on
+// bsr_attention_impl.h, topk_impl.h, semi_impl.h).  Every product is C[m][n] = sum_k X[m][k] * Y[n][k] over two LDS images, each row with one 16-byte pad, on
 // 16 x 16 tiles.  MFMA lane maps (cdna_hip_programming.md §3), lane l = (r, q) = (l & 15, l >> 4):
 //   f32  16x16x4f32:  lane l holds X[r][k0 + q] and Y[r][k0 + q];              C: col = r, row = 4 q + reg
 //   f64  16x16x4f64:  A/B as f32;                                             C: col = r, row = q + 4 reg
 //   bf16 16x16x32:    lane l holds X[r][k0 + 8 q + j], j < 8 (and Y alike);    C as f32
 // The f32 form is bit for bit a k-ordered fmaf chain; the bf16 form multiplies exactly and accumulates in fp32.
+// The 2:4 sparse form v_smfmac_f32_16x16x32_bf16 (smfmac_16x16x32 below; established with one-hot operands, all 64 lanes x 4
+// elements x 4 position values x 4 abid agree, EXPERIMENTS.md §32):
+//   X is compressed: lane l holds the FOUR kept values e = 0 .. 3 of X[r][k0 + 8 q .. + 8): e = 0, 1 belong to the group of four
+//   dense k at k0 + 8 q, e = 2, 3 to the group at k0 + 8 q + 4, each pair in ascending k.  Y and C are those of the dense bf16 form.
+//   idx: with cbsz = 0 the instruction reads byte `abid` (0 .. 3) of the lane's own idx register; bits [2 e + 1 : 2 e] of that byte
+//   are the position of value e INSIDE its group, so value e multiplies Y[n][k0 + 8 q + 4 (e / 2) + bits].  The other three
+//   bytes are ignored: one register serves the four instructions of a 128-wide stage.
 #pragma once
 
 #include "tsgu_common.h"
@@ -165,6 +172,15 @@ __device__ __forceinline__ void mfma_step(typename MfmaT<V>::Acc (&acc)[MT][NT],
                 if (nt < n_cnt) acc[mt][nt] = mfma_16x16<V>(xa, yb[nt], acc[mt][nt]);
         }
     }
+}
+
+// c + a · bᵀ with a 2:4 sparse `a` on one 16 x 16 tile over 32 dense k: `a` is the lane's four kept values, `idx` its position
+// register, of which the instruction reads byte ABID (the header comment has the maps).  semi_impl.h is the one user.
+typedef __bf16 mfma_bf16x4 __attribute__((ext_vector_type(4)));
+template <int ABID>
+__device__ __forceinline__ mfma_f32x4 smfmac_16x16x32(mfma_bf16x4 a, mfma_bf16x8 b, mfma_f32x4 c, int idx, std::integral_constant<int, ABID>) {
+    static_assert(ABID >= 0 && ABID < 4, "one of the four position bytes");
+    return __builtin_amdgcn_smfmac_f32_16x16x32_bf16(a, b, c, idx, 0, ABID);
 }
 
 // Row inside a 16 x 16 MFMA result of accumulator register `reg` on lane `lane` (its column: lane & 15).
