@@ -5,7 +5,8 @@ Drop-in names for ``sparse_mm`` / ``gather_mm`` / ``segment_mm`` / ``sparse_tria
 and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``sparse_mm_reduce`` / ``sparse_spgemm`` / ``sparse_bsr_mm`` /
 ``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
 ``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
-``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` beside them;
+``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` /
+``sparse_sinkhorn`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -26,6 +27,7 @@ from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_lo
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
 from .sparse_mm_reduce import SparseMMReduce, sparse_mm_reduce
+from .sparse_sinkhorn import SparseSinkhorn, sparse_sinkhorn
 from .sparse_softmax import SparseSoftmax, sparse_log_softmax, sparse_softmax
 from .sparse_spgemm import SparseSpGEMM, sparse_spgemm
 from .sparse_sqrt import SparseInvSqrtMM, sparse_inv_sqrt_mm, sparse_sqrt_mm
@@ -89,6 +91,8 @@ __all__ = [
     "sparse_bidir_logsumexp",
     "sparse_softmax",
     "sparse_log_softmax",
+    "sparse_sinkhorn",
+    "SparseSinkhorn",
     "sparse_attention",
     "SparseGenericLstsq",
     "wait_for_plans",

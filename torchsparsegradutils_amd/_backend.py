@@ -381,6 +381,21 @@ SIGNATURES_SEMI = {
 # it against the header)
 STAGED_SEMI = {"tsgu_hip_semi.h": SIGNATURES_SEMI}
 
+# the additive entries of csrc/tsgu_hip_sinkhorn.h (same library, same ABI version): the tenth STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI` and the nine registries above)
+SIGNATURES_SINKHORN = {
+    "tsgu_sinkhorn_workspace": (_int, [_int, _i64, ctypes.POINTER(_i64)]),
+    "tsgu_sinkhorn_half": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_sinkhorn_plan": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_sinkhorn_half_backward": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int,
+                                           _ptr, _i64, _int, _ptr]),
+    "tsgu_segment_sum": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_sinkhorn_cpu.py holds it
+# against the header)
+STAGED_SINKHORN = {"tsgu_hip_sinkhorn.h": SIGNATURES_SINKHORN}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -405,7 +420,7 @@ def load_library():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
-                      *STAGED_TOPK.values(), *STAGED_SEMI.values()):
+                      *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1023,6 +1038,78 @@ def segment_softmax(ptr, perm, val, n_groups: int, log_form: bool, crossing: boo
 def segment_softmax_backward(ptr, perm, y, g, n_groups: int, log_form: bool, crossing: bool, out=None):
     """gin = y·(g − Σ_group g·y), or g − exp(y)·Σ_group g for the log form, in the values' own order."""
     return _softmax_call("tsgu_segment_softmax_backward", ptr, perm, (y, g), n_groups, log_form, crossing, out)
+
+
+def sinkhorn_workspace_bytes(dtype: torch.dtype, nnz: int) -> int:
+    """Workspace bytes the Sinkhorn entries need for `nnz` entries of value type `dtype` when groups cross ranges."""
+    return _query("tsgu_sinkhorn_workspace", _VTYPE[dtype], nnz)[0]
+
+
+def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.float32 if dtype == torch.bfloat16 else dtype
+
+
+def _sinkhorn_operands(what: str, dev, val, index, vectors, workspace):
+    """The refusals the Sinkhorn wrappers share: `index` [(tensor, entries)] of one dtype, `vectors` [(tensor or None, entries)] of
+    the values' accumulator type; everything contiguous.  Returns the workspace's bytes (0 without one)."""
+    acc = _acc_dtype(val.dtype)
+    if not val.is_contiguous():
+        raise RuntimeError(f"{what}: the value array must be contiguous")
+    idt = index[0][0].dtype
+    for t, n in index:
+        if t is not None and (t.dtype != idt or not t.is_contiguous() or t.numel() != n):
+            raise RuntimeError(f"{what}: index arrays must be contiguous, of one dtype and of their pattern's sizes")
+    for t, n in vectors:
+        if t is not None and (t.dtype != acc or not t.is_contiguous() or t.numel() != n):
+            raise RuntimeError(f"{what}: group vectors must be contiguous, of dtype {acc} and of their direction's length")
+    if workspace is not None and workspace.numel() * workspace.element_size() < sinkhorn_workspace_bytes(val.dtype, val.numel()):
+        raise RuntimeError(f"{what}: the workspace is too small")
+    return 0 if workspace is None else workspace.numel() * workspace.element_size()
+
+
+def sinkhorn_half(ptr, perm, idx, val, other, log_marg, out, workspace):
+    """out[g] = log_marg[g] − log Σ_{k in group g} exp(val[perm[k]] + other[idx[k]]) over the segments of `ptr` (log_marg None: zeros).
+    `out` may be a row of a larger buffer.  `workspace` None: the caller knows that no group crosses a range of the kernels."""
+    dev = require_device(ptr, perm, idx, val, other, log_marg, out, workspace)
+    n, nnz = ptr.numel() - 1, val.numel()
+    wsb = _sinkhorn_operands("sinkhorn_half", dev, val, [(ptr, n + 1), (perm, nnz), (idx, nnz)],
+                             [(log_marg, n), (out, n), (other, other.numel())], workspace)
+    launch("tsgu_sinkhorn_half", dev, vtype_of(val), itype_of(ptr), n, nnz, ptr, perm, idx, val, other, log_marg, out, workspace, wsb)
+
+
+def sinkhorn_plan(ptr, idx, val, pot_group, pot_other, out=None):
+    """out[k] = val[k] + pot_group[group of k] + pot_other[idx[k]] in stored order, rounded once to the values' dtype."""
+    if out is None:
+        out = torch.empty_like(val)
+    dev = require_device(ptr, idx, val, pot_group, pot_other, out)
+    n, nnz = ptr.numel() - 1, val.numel()
+    _sinkhorn_operands("sinkhorn_plan", dev, val, [(ptr, n + 1), (idx, nnz)], [(pot_group, n), (pot_other, pot_other.numel())], None)
+    if out.dtype != val.dtype or out.shape != val.shape or not out.is_contiguous():
+        raise RuntimeError("sinkhorn_plan: the output must be a contiguous array of the values' dtype and shape")
+    launch("tsgu_sinkhorn_plan", dev, vtype_of(val), itype_of(ptr), n, nnz, ptr, idx, val, pot_group, pot_other, out)
+    return out
+
+
+def sinkhorn_half_backward(ptr, perm, idx, grp, val, pot_group, pot_other, log_marg_other, g_other, grad, g_out, accumulate: bool,
+                           workspace):
+    """The adjoint of the other direction's half step, walked over the segments of `ptr`: term = g_other[idx]·exp(val + pot_group +
+    pot_other[idx] − log_marg_other[idx]); grad[perm[k]] −= term; g_out[g] = (accumulate ? g_out[g] : 0) − Σ_group term."""
+    dev = require_device(ptr, perm, idx, grp, val, pot_group, pot_other, log_marg_other, g_other, grad, g_out, workspace)
+    n, nnz, m = ptr.numel() - 1, val.numel(), g_other.numel()
+    wsb = _sinkhorn_operands("sinkhorn_half_backward", dev, val, [(ptr, n + 1), (perm, nnz), (idx, nnz), (grp, nnz)],
+                             [(pot_group, n), (g_out, n), (pot_other, m), (log_marg_other, m), (g_other, m), (grad, nnz)], workspace)
+    launch("tsgu_sinkhorn_half_backward", dev, vtype_of(val), itype_of(ptr), n, nnz, ptr, perm, idx, grp, val, pot_group, pot_other,
+           log_marg_other, g_other, grad, g_out, int(bool(accumulate)), workspace, wsb)
+
+
+def segment_sum(ptr, perm, val, add, out, workspace):
+    """out[g] = add[g] + Σ_{k in group g} val[perm[k]] (add None: zeros); val is an accumulator array (float32 / float64)."""
+    dev = require_device(ptr, perm, val, add, out, workspace)
+    n, nnz = ptr.numel() - 1, val.numel()
+    if val.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"segment_sum: values must be float32 or float64, got {val.dtype}")
+    wsb = _sinkhorn_operands("segment_sum", dev, val, [(ptr, n + 1), (perm, nnz)], [(add, n), (out, n)], workspace)
+    launch("tsgu_segment_sum", dev, vtype_of(val), itype_of(ptr), n, nnz, ptr, perm, val, add, out, workspace, wsb)
 
 
 def attention_supported(dtype: torch.dtype, heads: int, d: int) -> bool:

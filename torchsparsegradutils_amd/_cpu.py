@@ -1023,3 +1023,88 @@ def semi_mm_backward(values, cols, k: int, Y, G, linear: bool, need_values: bool
         A = semi_dense(values, cols, k, acc)
         ddense = (Ga @ A if linear else A.t() @ Ga).to(values.dtype)
     return dvalues, ddense
+
+
+# ---- sparse_sinkhorn (sparse_sinkhorn.py): a direction is (ptr, perm, idx, grp, n groups, ...) ------------------------------------
+def _sk_at(d, v: torch.Tensor) -> torch.Tensor:
+    """The values in the direction's walking order."""
+    return v if d.perm is None else v.index_select(0, d.perm.to(torch.int64))
+
+
+def _sk_half(d, v: torch.Tensor, other: torch.Tensor, log_marg) -> torch.Tensor:
+    """log_marg − LSE over the direction's groups of (value + the other side's potential); an empty group gives +inf."""
+    x = _sk_at(d, v)
+    # (a stored −inf is an absent entry, also beside the +inf potential of a group that holds nothing else)
+    x = torch.where(x == float("-inf"), x, x + other[d.idx.to(torch.int64)])
+    lse = segment_logsumexp(d.ptr, None, x, d.n, False, 0)
+    return -lse if log_marg is None else log_marg - lse
+
+
+def _sk_potential(log_marg, neg_lse: torch.Tensor) -> torch.Tensor:
+    """The potential of a half step from what it keeps: log_marg − lse (the same rounding as the subtraction)."""
+    return neg_lse if log_marg is None else log_marg + neg_lse
+
+
+def sinkhorn_forward(rowd, cold, val: torch.Tensor, log_a, log_b, T: int, keep: bool):
+    """(NU, NV, u^T, v^T) of the T iterations from v⁰ = 0: NU[t − 1] = −LSE_row(S + v^{t−1}) and NV[t − 1] = −LSE_col(S + u^t), the
+    potentials less their log marginals, when `keep` (else None).  Accumulator precision (float32 for bfloat16 values)."""
+    _cpu_only(val, log_a, log_b)
+    acc = torch.float32 if val.dtype == torch.bfloat16 else val.dtype
+    x = val.reshape(-1).to(acc)
+    NU = torch.empty((T, rowd.n), dtype=acc) if keep else None
+    NV = torch.empty((T, cold.n), dtype=acc) if keep else None
+    v = torch.zeros(cold.n, dtype=acc)
+    for t in range(T):
+        nu = _sk_half(rowd, x, v, None)
+        u = _sk_potential(log_a, nu)
+        nv = _sk_half(cold, x, u, None)
+        v = _sk_potential(log_b, nv)
+        if keep:
+            NU[t], NV[t] = nu, nv
+    return NU, NV, u, v
+
+
+def sinkhorn_plan(grp: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, pot_group: torch.Tensor, pot_other: torch.Tensor) -> torch.Tensor:
+    """val + pot_group[grp] + pot_other[idx] in stored order, rounded once to the values' dtype."""
+    _cpu_only(val, pot_group, pot_other)
+    v = val.reshape(-1).to(pot_group.dtype)
+    # (a stored −inf stays −inf, also beside the +inf potential of a group that holds nothing else)
+    return torch.where(v == float("-inf"), v, (v + pot_group[grp.to(torch.int64)]) + pot_other[idx.to(torch.int64)]).to(val.dtype)
+
+
+def _sk_half_backward(d, v, pot_group, pot_other, log_marg_other, g_other, dS) -> torch.Tensor:
+    """term = g_other[idx]·exp(value + pot_group[grp] + pot_other[idx] − log_marg_other[idx]); dS −= term at the entries' own
+    positions; returns −Σ_group term.  With pot_other = −lse of the other direction's half step (and no log marginal) the argument
+    is that step's own staged value less its own lse."""
+    j, g = d.idx.to(torch.int64), d.grp.to(torch.int64)
+    x = (_sk_at(d, v) + pot_group[g]) + pot_other[j]
+    if log_marg_other is not None:
+        x = x - log_marg_other[j]
+    term = torch.where(_sk_at(d, v) == float("-inf"), torch.zeros_like(x), g_other[j] * x.exp())   # (a stored −inf: absent)
+    if d.perm is None:
+        dS -= term
+    else:
+        dS.index_add_(0, d.perm.to(torch.int64), term, alpha=-1)
+    return torch.zeros(d.n, dtype=v.dtype).index_add_(0, g, term).neg_()
+
+
+def sinkhorn_backward(rowd, cold, val, log_a, log_b, NU, NV, dS, gu, gv, T: int):
+    """The reverse sweep of `sinkhorn_forward`: dS comes in as the cotangent of log_P (accumulator precision, stored order) and
+    leaves as the gradient of the values; returns (dlog_a, dlog_b)."""
+    _cpu_only(val, NU, NV, dS)
+    v = val.reshape(-1).to(NU.dtype)
+    ub = torch.zeros(rowd.n, dtype=NU.dtype).index_add_(0, rowd.grp.to(torch.int64), _sk_at(rowd, dS))
+    vb = torch.zeros(cold.n, dtype=NU.dtype).index_add_(0, cold.grp.to(torch.int64), _sk_at(cold, dS))
+    if gu is not None:
+        ub += gu
+    if gv is not None:
+        vb += gv
+    dla, dlb = torch.zeros_like(ub), torch.zeros_like(vb)
+    for t in range(T, 0, -1):
+        dlb += vb
+        u_t = _sk_potential(log_a, NU[t - 1])
+        v_before = _sk_potential(log_b, NV[t - 2]) if t > 1 else torch.zeros_like(vb)
+        ub = _sk_half_backward(rowd, v, u_t, NV[t - 1], None, vb, dS) + (ub if t == T else 0)
+        dla += ub
+        vb = _sk_half_backward(cold, v, v_before, NU[t - 1], None, ub, dS)
+    return dla, dlb
