@@ -396,6 +396,22 @@ SIGNATURES_SINKHORN = {
 # against the header)
 STAGED_SINKHORN = {"tsgu_hip_sinkhorn.h": SIGNATURES_SINKHORN}
 
+# the additive entries of csrc/tsgu_hip_semiring.h (same library, same ABI version): the eleventh STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI` and the ten registries above)
+SIGNATURES_SEMIRING = {
+    "tsgu_semiring_geometry": (_int, [_int, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_semiring_mm": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr,
+                                    _i64, _int, _ptr]),
+    "tsgu_csr_semiring_mm_bwd_values": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64,
+                                               _ptr, _i64, _i64, _ptr, _int, _ptr]),
+    "tsgu_csr_semiring_mm_bwd_dense": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr,
+                                              _i64, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_semiring_cpu.py holds it
+# against the header)
+STAGED_SEMIRING = {"tsgu_hip_semiring.h": SIGNATURES_SEMIRING}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -420,7 +436,8 @@ def load_library():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
-                      *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values()):
+                      *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
+                      *STAGED_SEMIRING.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1251,6 +1268,73 @@ def csr_spmm_reduce_backward_dense(tptr, tidx, perm, val, arg, G, n_rows: int, n
     dB = torch.empty((n_cols, p), dtype=G.dtype, device=dev)
     launch("tsgu_csr_spmm_reduce_backward_dense", dev, vtype_of(G), itype_of(tptr), n_rows, n_cols, tidx.numel(), tptr, tidx, perm,
            val, arg, _ld(arg), G, _ld(G), p, dB, p)
+    return dB
+
+
+SEMIRINGS = {"log": 0, "max_plus": 1, "min_plus": 2}
+
+
+def semiring_geometry(dtype: torch.dtype, p: int):
+    """(rows per workgroup, entries of one staging pass, columns per grid.z slice) of the semiring product kernels for `p` columns
+    of value type `dtype` with 16-byte aligned operands: the sizes at which their walk changes path.  Host only."""
+    return _query("tsgu_semiring_geometry", _VTYPE[dtype], int(p))
+
+
+def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def _semiring_operands(index_arrays, val, dense, C_acc=None, arg=None):
+    dev = require_device(*index_arrays, val, *dense, C_acc, arg)
+    _one_dtype("index arrays of a semiring product", index_arrays)
+    ref = _one_width("dense operands of a semiring product", dense)
+    if val is not None and (val.dtype != ref.dtype or val.dim() != 1 or not val.is_contiguous()):
+        raise RuntimeError(f"expected A and B to have the same dtype, got {val.dtype} and {ref.dtype}")
+    for t, dtype, what in ((C_acc, _acc_dtype(ref.dtype), "C in the accumulator type"), (arg, torch.int32, "arg")):
+        if t is not None and (t.dtype != dtype or t.dim() != 2 or t.size(1) != ref.size(1) or (t.stride(1) != 1 and t.size(1) > 1)):
+            raise RuntimeError(f"a semiring product expects {what} as a row-major {dtype} matrix of {ref.size(1)} columns")
+    return dev
+
+
+def csr_semiring_mm(crow, col, val, B, n_rows: int, n_cols: int, semiring: str, want_acc: bool = False):
+    """(C [n_rows, p], C_acc or None, arg or None) of the product of the 2-D CSR arrays with B [n_cols, p] in `semiring`.  log: C_acc is
+    C in the accumulator type — C itself for float32 / float64, a float32 copy written in the same pass for bfloat16 when `want_acc`.
+    Tropical: arg [n_rows, p] int32 is the winning entry's position in `val` (−1 for a row without entries)."""
+    dev = _semiring_operands((crow, col), val, (B,))
+    p = B.size(1)
+    if p < 1:
+        raise RuntimeError("a semiring product needs at least one column")
+    sr = SEMIRINGS[semiring]
+    C = torch.empty((n_rows, p), dtype=B.dtype, device=dev)
+    C_acc = arg = None
+    if sr == 0:
+        if want_acc:
+            C_acc = C if C.dtype == _acc_dtype(C.dtype) else torch.empty((n_rows, p), dtype=torch.float32, device=dev)
+    else:
+        arg = torch.empty((n_rows, p), dtype=torch.int32, device=dev)
+    launch("tsgu_csr_semiring_mm", dev, vtype_of(B), itype_of(crow), sr, n_rows, n_cols, col.numel(), crow, col, val, B, _ld(B), p,
+           C, p, None if C_acc is C else C_acc, p, arg, p)
+    return C, C_acc, arg
+
+
+def csr_semiring_mm_bwd_values(crow, col, val, B, C_acc, arg, G, n_rows: int, n_cols: int, semiring: str):
+    """dval[e] = Σ_c G[i,c]·W[e,c], in the order of the value array: W from (val, B, C_acc) for log, from arg for the tropical ones."""
+    dev = _semiring_operands((crow, col), val, (G, B), C_acc, arg)
+    dval = torch.empty((col.numel(),), dtype=G.dtype, device=dev)
+    launch("tsgu_csr_semiring_mm_bwd_values", dev, vtype_of(G), itype_of(crow), SEMIRINGS[semiring], n_rows, n_cols, col.numel(), crow,
+           col, val, B, _ld(B), C_acc, 0 if C_acc is None else _ld(C_acc), arg, 0 if arg is None else _ld(arg), G, _ld(G), G.size(1),
+           dval)
+    return dval
+
+
+def csr_semiring_mm_bwd_dense(tptr, tidx, perm, val, B, C_acc, arg, G, n_rows: int, n_cols: int, semiring: str):
+    """dB[j,c] = Σ_{e in column j} G[i,c]·W[e,c] over the transposed walk (tptr, tidx, perm into val)."""
+    dev = _semiring_operands((tptr, tidx, perm), val, (G, B), C_acc, arg)
+    p = G.size(1)
+    dB = torch.empty((n_cols, p), dtype=G.dtype, device=dev)
+    launch("tsgu_csr_semiring_mm_bwd_dense", dev, vtype_of(G), itype_of(tptr), SEMIRINGS[semiring], n_rows, n_cols, tidx.numel(), tptr,
+           tidx, perm, val, B, _ld(B), C_acc, 0 if C_acc is None else _ld(C_acc), arg, 0 if arg is None else _ld(arg), G, _ld(G), p,
+           dB, p)
     return dB
 
 

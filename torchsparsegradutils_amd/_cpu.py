@@ -387,6 +387,62 @@ def mm_reduce_backward(crow, col, values, B, shape, reduce: str, G, need_a: bool
     return ga, gb
 
 
+def _semiring_candidates(crow, col, values, B):
+    """(row of every entry, column of every entry, t = val + B[col] in the accumulator type: nnz × p)."""
+    acc = torch.float64 if B.dtype == torch.float64 else torch.float32
+    counts = (crow[1:] - crow[:-1]).to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(counts.numel()), counts)
+    cols = col.to(torch.int64)
+    return rows, cols, values.to(acc).unsqueeze(1) + B.to(acc).index_select(0, cols)
+
+
+def _semiring_forward(rows, T, n: int, semiring: str):
+    """(C, arg or None) in the accumulator type from the candidates T of the entries' rows."""
+    nnz, p = T.shape
+    idx = rows.unsqueeze(1).expand(nnz, p)
+    inf = float("inf")
+    if semiring == "log":
+        M = torch.full((n, p), -inf, dtype=T.dtype).scatter_reduce(0, idx, T, "amax", include_self=True)
+        shift = torch.where(torch.isfinite(M), M, torch.zeros_like(M))
+        S = torch.zeros((n, p), dtype=T.dtype).index_add_(0, rows, torch.exp(T - shift.index_select(0, rows)))
+        return torch.log(S) + shift, None
+    worst = inf if semiring == "min_plus" else -inf
+    M = torch.full((n, p), worst, dtype=T.dtype).scatter_reduce(0, idx, T, "amin" if semiring == "min_plus" else "amax", include_self=True)
+    Mr = M.index_select(0, rows)
+    wins = (T == Mr) | (torch.isnan(T) & torch.isnan(Mr))           # the first stored of these is the winner
+    pos = torch.arange(nnz, dtype=torch.int64).unsqueeze(1).expand(nnz, p)
+    arg = torch.full((n, p), nnz, dtype=torch.int64).scatter_reduce(0, idx, torch.where(wins, pos, nnz), "amin", include_self=True)
+    has = arg < nnz
+    C = torch.where(has, T.gather(0, arg.clamp(max=max(nnz - 1, 0))), M) if nnz else M
+    return C, torch.where(has, arg, -1).to(torch.int32)
+
+
+def semiring_mm(crow, col, values, B, shape, semiring: str):
+    """(C, arg or None) of the sparse × dense product in the log, max-plus or min-plus semiring for the 2-D CSR arrays of A: a gather,
+    a ``scatter_reduce`` and an ``index_add``, with the semantics the HIP kernels of csrc/semiring.hip restate (candidates in the
+    accumulator type, first stored winner, −inf candidates absent).  Keeps an nnz × p temporary."""
+    _cpu_only(crow, col, values, B)
+    rows, _, T = _semiring_candidates(crow, col, values.detach(), B.detach())
+    C, arg = _semiring_forward(rows, T, shape[0], semiring)
+    return C.to(B.dtype), arg
+
+
+def semiring_mm_backward(crow, col, values, B, shape, semiring: str, G, need_a: bool, need_b: bool):
+    """(gradient of the values or None, gradient of B or None) of :func:`semiring_mm`; the forward is evaluated again."""
+    _cpu_only(crow, col, values, B, G)
+    rows, cols, T = _semiring_candidates(crow, col, values.detach(), B.detach())
+    C, arg = _semiring_forward(rows, T, shape[0], semiring)
+    if semiring == "log":
+        W = torch.where(T == -float("inf"), torch.zeros_like(T), torch.exp(T - C.index_select(0, rows)))
+    else:
+        W = arg.index_select(0, rows) == torch.arange(T.size(0), dtype=torch.int32).unsqueeze(1)
+    Gr = G.to(T.dtype).index_select(0, rows)
+    GW = torch.where(T == -float("inf"), torch.zeros_like(T), Gr * W) if semiring == "log" else torch.where(W, Gr, torch.zeros_like(Gr))
+    ga = GW.sum(1).to(B.dtype) if need_a else None
+    gb = torch.zeros((shape[1], T.size(1)), dtype=T.dtype).index_add_(0, cols, GW).to(B.dtype) if need_b else None
+    return ga, gb
+
+
 def spgemm(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     """``torch.sparse.mm(A, B)`` of two coalesced COO operands (float32 or float64): the structural product, coalesced."""
     _cpu_only(A, B)
