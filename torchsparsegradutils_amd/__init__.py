@@ -6,7 +6,7 @@ and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``spars
 ``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
 ``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
 ``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` /
-``sparse_sinkhorn`` / ``sparse_semiring_mm`` beside them;
+``sparse_sinkhorn`` / ``sparse_semiring_mm`` / ``sparse_gat_attention`` / ``sparse_gatv2_attention`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -24,6 +24,7 @@ from .sparse_fsai import SparseFSAI, sparse_fsai
 from .sparse_lobpcg import SparseLOBPCG, sparse_lobpcg
 from .sparse_logdet import SparseLogDet, sparse_inv_quad_logdet, sparse_logdet
 from .sparse_logsumexp import SparseLogSumExp, sparse_bidir_logsumexp, sparse_logsumexp
+from .sparse_gat import SparseGATAttention, SparseGATv2Attention, sparse_gat_attention, sparse_gatv2_attention
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
 from .sparse_mm_reduce import SparseMMReduce, sparse_mm_reduce
@@ -96,6 +97,10 @@ __all__ = [
     "SparseSinkhorn",
     "sparse_semiring_mm",
     "SparseSemiringMM",
+    "sparse_gat_attention",
+    "sparse_gatv2_attention",
+    "SparseGATAttention",
+    "SparseGATv2Attention",
     "sparse_attention",
     "SparseGenericLstsq",
     "wait_for_plans",

@@ -412,6 +412,23 @@ SIGNATURES_SEMIRING = {
 # against the header)
 STAGED_SEMIRING = {"tsgu_hip_semiring.h": SIGNATURES_SEMIRING}
 
+# the additive entries of csrc/tsgu_hip_gat.h (same library, same ABI version): the twelfth STAGED header, in a registry of its own
+# for the same reason (tests pin `ABI` and the eleven registries above)
+SIGNATURES_GAT = {
+    "tsgu_gat_geometry": (_int, [_int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_gat_forward": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr,
+                                    _int, _int, _dbl, _ptr, _i64, _ptr, _int, _ptr]),
+    "tsgu_csr_gat_backward_rows": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
+                                          _ptr, _ptr, _i64, _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_csr_gat_backward_cols": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
+                                          _ptr, _ptr, _i64, _ptr, _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _int, _ptr]),
+    "tsgu_gat_fold": (_int, [_int, _ptr, _i64, _int, _int, _ptr, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_gat_cpu.py holds it against
+# the header)
+STAGED_GAT = {"tsgu_hip_gat.h": SIGNATURES_GAT}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -437,7 +454,7 @@ def load_library():
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
                       *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
-                      *STAGED_SEMIRING.values()):
+                      *STAGED_SEMIRING.values(), *STAGED_GAT.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1336,6 +1353,99 @@ def csr_semiring_mm_bwd_dense(tptr, tidx, perm, val, B, C_acc, arg, G, n_rows: i
            tidx, perm, val, B, _ld(B), C_acc, 0 if C_acc is None else _ld(C_acc), arg, 0 if arg is None else _ld(arg), G, _ld(G), p,
            dB, p)
     return dB
+
+
+GAT_KINDS = {"gat": 0, "gatv2": 1}
+
+
+def gat_supported(dtype: torch.dtype, heads: int, d: int) -> bool:
+    """Do the graph-attention kernels take `heads` heads of width `d` in value type `dtype`?  Host only (no GPU needed)."""
+    vt = _VTYPE.get(dtype)
+    if vt is None:
+        return False
+    outs = [_int(0) for _ in range(3)]
+    return load_library().tsgu_gat_geometry(vt, 0, int(heads), int(d), *map(ctypes.byref, outs)) == 0
+
+
+def gat_geometry(dtype: torch.dtype, kind: str, heads: int, d: int):
+    """(rows per workgroup, entries of one staged slice of the forward, elements of a dense row one tile covers) of the
+    graph-attention kernels of `kind` ("gat" / "gatv2") for (dtype, heads, d): the sizes at which their walk changes path.  Host only."""
+    return _query("tsgu_gat_geometry", _VTYPE[dtype], GAT_KINDS[kind], int(heads), int(d))
+
+
+def _gat_operands(kind: str, walk, bias, scalars, dense, att, heads: int, d: int):
+    """Operand check of one graph-attention launch: the walk and the dense rows as `_attention_walk`, the per-head scalars as
+    contiguous [rows, heads] arrays and att as a contiguous, 16-byte aligned [heads·d] array of the dense operands' dtype."""
+    dev = _attention_walk(walk, bias, *dense)
+    require_device(*scalars, att)
+    ref = dense[0]
+    if ref.size(1) != heads * d:
+        raise RuntimeError(f"the dense operands of a graph attention must be [rows, heads*d] = [rows, {heads * d}], got {tuple(ref.shape)}")
+    for t in scalars:
+        if t.dtype != ref.dtype or t.dim() != 2 or t.size(1) != heads or not t.is_contiguous():
+            raise RuntimeError(f"s_dst and s_src must be contiguous [rows, {heads}] arrays in the operands' dtype")
+    if (att is None) != (kind == "gat") or (att is not None and (
+            att.dtype != ref.dtype or att.numel() != heads * d or not att.is_contiguous() or att.data_ptr() % 16)):
+        raise RuntimeError(f"att must be a contiguous, 16-byte aligned [{heads}, {d}] array in the operands' dtype (GATv2 only)")
+    return dev
+
+
+def csr_gat_forward(kind: str, walk, bias, s_dst, s_src, X_dst, X_src, att, heads: int, d: int, slope: float):
+    """(O [n, heads·d], lse [n, heads] in the accumulator type) of a GAT (`kind` "gat": s_dst [n, heads], s_src [m, heads], the
+    messages X_src = V [m, heads·d]; X_dst, att None) or GATv2 ("gatv2": X_dst [n, heads·d], X_src [m, heads·d], att [heads·d];
+    s_dst, s_src None) layer over the pattern walked by rows as ``walk = (ptr, idx, perm or None)``; bias as `csr_attention`."""
+    v2 = kind == "gatv2"
+    X_src = _aligned_rows(X_src)
+    X_dst = _aligned_rows(X_dst) if v2 else None
+    dev = _gat_operands(kind, walk, bias, () if v2 else (s_dst, s_src), (X_src, X_dst) if v2 else (X_src,), att, heads, d)
+    ptr, idx, perm = walk
+    n, m = ptr.numel() - 1, X_src.size(0)
+    O = torch.empty((n, heads * d), dtype=X_src.dtype, device=dev)
+    lse = torch.empty((n, heads), dtype=_acc_dtype(X_src.dtype), device=dev)
+    launch("tsgu_csr_gat_forward", dev, vtype_of(X_src), itype_of(ptr), GAT_KINDS[kind], n, m, idx.numel(), ptr, idx, perm, bias,
+           s_dst, s_src, X_dst, _ld(X_dst) if v2 else 0, X_src, _ld(X_src), att, heads, d, float(slope), O, _ld(O), lse)
+    return O, lse
+
+
+def csr_gat_backward(kind: str, walk, twalk, bias, s_dst, s_src, X_dst, X_src, att, dO, lse, heads: int, d: int, slope: float,
+                     want_dA: bool):
+    """(d_dst, d_src, ds_src or None, datt or None, dA or None) from the forward's lse: the row pass over `walk`, the column pass
+    over the transposed walk `twalk`, and for GATv2 the fold of the workgroups' shares of datt, on one stream.  GAT: d_dst = ds_dst
+    [n, heads], d_src = dV; GATv2: d_dst = dX_dst, d_src = dX_src.  dA is in the accumulator type, in the order of the pattern's
+    value array."""
+    v2 = kind == "gatv2"
+    X_src, dO = _aligned_rows(X_src), _aligned_rows(dO)
+    X_dst = _aligned_rows(X_dst) if v2 else None
+    dense = (X_src, dO, X_dst) if v2 else (X_src, dO)
+    dev = _gat_operands(kind, walk, bias, () if v2 else (s_dst, s_src), dense, att, heads, d)
+    _attention_walk(twalk, bias, *dense)
+    ptr, idx, perm = walk
+    tptr, tidx, tperm = twalk
+    n, m, nnz, w = ptr.numel() - 1, X_src.size(0), idx.numel(), heads * d
+    acc = _acc_dtype(X_src.dtype)
+    if lse.dtype != acc or lse.shape != (n, heads) or not lse.is_contiguous():
+        raise RuntimeError("lse must be the forward's [n, heads] array in the accumulator type")
+    kw = dict(dtype=X_src.dtype, device=dev)
+    d_dst = torch.empty((n, w if v2 else heads), **kw)
+    d_src = torch.empty((m, w), **kw)
+    ds_src = None if v2 else torch.empty((m, heads), **kw)
+    delta = torch.empty((n, heads), dtype=acc, device=dev)
+    dA = torch.empty((nnz,), dtype=acc, device=dev) if want_dA else None
+    partials, n_part, datt = None, 0, None
+    if v2:
+        rpb = gat_geometry(X_src.dtype, kind, heads, d)[0]
+        n_part = (n + rpb - 1) // rpb
+        partials = torch.empty((max(n_part, 1), w), dtype=acc, device=dev)
+        datt = torch.empty((w,), **kw)
+    vt, it, k = vtype_of(X_src), itype_of(ptr), GAT_KINDS[kind]
+    ldxd = _ld(X_dst) if v2 else 0
+    launch("tsgu_csr_gat_backward_rows", dev, vt, it, k, n, m, nnz, ptr, idx, perm, bias, s_dst, s_src, X_dst, ldxd, X_src, _ld(X_src),
+           att, dO, _ld(dO), lse, heads, d, float(slope), d_dst, _ld(d_dst), delta, dA, partials, n_part)
+    launch("tsgu_csr_gat_backward_cols", dev, vt, it, k, n, m, nnz, tptr, tidx, tperm, bias, s_dst, s_src, X_dst, ldxd, X_src,
+           _ld(X_src), att, dO, _ld(dO), lse, delta, heads, d, float(slope), d_src, _ld(d_src), ds_src)
+    if v2:
+        launch("tsgu_gat_fold", dev, vt, partials, n_part, heads, d, datt)
+    return d_dst, d_src, ds_src, datt, dA
 
 
 def bsr_mm_geometry(dtype: torch.dtype, bh: int, bw: int, p: int):

@@ -234,6 +234,67 @@ def attention_backward(ptr, idx, perm, Q, K, V, dO, P, heads: int, scale: float,
     return dQ.view(n, -1).to(Q.dtype), dK.view(m, -1).to(Q.dtype), dV.view(m, -1).to(Q.dtype), dA
 
 
+def _gat_terms(kind: str, ptr, idx, perm, bias, s_dst, s_src, X_dst, X_src, att, heads: int, slope: float):
+    """(row of every entry, its column, the LeakyReLU's argument z — [nnz, heads] for "gat", [nnz, heads, d] for "gatv2" — and
+    the logits [nnz, heads]) of the walk (ptr, idx, perm) in the accumulator type."""
+    acc = torch.float32 if X_src.dtype == torch.bfloat16 else X_src.dtype
+    n, nnz = ptr.numel() - 1, idx.numel()
+    rows, cols = _segment_ids(ptr, n, nnz), idx.reshape(-1).to(torch.int64)
+    if kind == "gat":
+        z = s_dst.to(acc).index_select(0, rows) + s_src.to(acc).index_select(0, cols)
+        t = torch.nn.functional.leaky_relu(z, slope)
+    else:
+        xd, xs = X_dst.to(acc).view(n, heads, -1), X_src.to(acc).view(X_src.size(0), heads, -1)
+        z = xd.index_select(0, rows) + xs.index_select(0, cols)
+        t = (att.to(acc).view(1, heads, -1) * torch.nn.functional.leaky_relu(z, slope)).sum(-1)
+    if bias is not None:
+        b = bias.reshape(-1) if perm is None else bias.reshape(-1).index_select(0, perm.to(torch.int64))
+        t = t + b.to(acc).unsqueeze(1)
+    return rows, cols, z, t
+
+
+def gat_attention(kind: str, ptr, idx, perm, bias, s_dst, s_src, X_dst, X_src, att, heads: int, slope: float):
+    """(O [n, heads·d], P [nnz, heads]) of a GAT ("gat": logits lrelu(s_dst[i] + s_src[j]), messages X_src = V) or GATv2 ("gatv2":
+    logits Σ_k att·lrelu(X_dst[i] + X_src[j]), messages X_src) layer over the pattern walked by rows as (ptr, idx, perm): gathers,
+    the segmented softmax of every head, index_add.  Special values as :func:`attention`.  Keeps nnz-sized temporaries."""
+    _cpu_only(ptr, idx, perm, bias, s_dst, s_src, X_dst, X_src, att)
+    n = ptr.numel() - 1
+    rows, cols, _, t = _gat_terms(kind, ptr, idx, perm, bias, s_dst, s_src, X_dst, X_src, att, heads, slope)
+    P = torch.stack([segment_softmax(ptr, None, t[:, h].contiguous(), n, False) for h in range(heads)], 1)
+    v = X_src.to(P.dtype).view(X_src.size(0), heads, -1)
+    O = torch.zeros((n, heads, v.size(-1)), dtype=P.dtype).index_add_(0, rows, P.unsqueeze(-1) * v.index_select(0, cols))
+    return O.view(n, -1).to(X_src.dtype), P
+
+
+def gat_attention_backward(kind: str, ptr, idx, perm, bias, s_dst, s_src, X_dst, X_src, att, dO, P, heads: int, slope: float,
+                           want_dA: bool):
+    """(d_dst, d_src, ds_src or None, datt or None, dA or None) of :func:`gat_attention` from its probabilities P: dP = <dO[i],
+    X_src[j]>, δ = Σ_j P·dP, dS = P·(dP − δ), then the chain through the LeakyReLU (derivative `slope` at 0).  "gat": d_dst =
+    ds_dst, d_src = dV; "gatv2": d_dst = dX_dst, d_src = dX_src."""
+    _cpu_only(ptr, idx, perm, bias, s_dst, s_src, X_dst, X_src, att, dO, P)
+    acc, dtype = P.dtype, X_src.dtype
+    n, m = ptr.numel() - 1, X_src.size(0)
+    rows, cols, z, _ = _gat_terms(kind, ptr, idx, perm, None, s_dst, s_src, X_dst, X_src, att, heads, slope)
+    v, g = X_src.to(acc).view(m, heads, -1), dO.to(acc).view(n, heads, -1)
+    gi = g.index_select(0, rows)
+    dP = (gi * v.index_select(0, cols)).sum(-1)
+    delta = torch.zeros((n, heads), dtype=acc).index_add_(0, rows, P * dP)
+    dS = P * (dP - delta.index_select(0, rows))
+    slope_of = torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope))
+    msg = torch.zeros_like(v).index_add_(0, cols, P.unsqueeze(-1) * gi)
+    dA = _from_plan_order(dS.sum(1), perm, acc) if want_dA else None
+    if kind == "gat":
+        gz = dS * slope_of
+        ds_dst = torch.zeros((n, heads), dtype=acc).index_add_(0, rows, gz)
+        ds_src = torch.zeros((m, heads), dtype=acc).index_add_(0, cols, gz)
+        return ds_dst.to(dtype), msg.view(m, -1).to(dtype), ds_src.to(dtype), None, dA
+    gz = dS.unsqueeze(-1) * att.to(acc).view(1, heads, -1) * slope_of
+    dX_dst = torch.zeros((n,) + v.shape[1:], dtype=acc).index_add_(0, rows, gz)
+    dX_src = msg.index_add_(0, cols, gz)
+    datt = (dS.unsqueeze(-1) * torch.nn.functional.leaky_relu(z, slope)).sum(0)
+    return dX_dst.view(n, -1).to(dtype), dX_src.view(m, -1).to(dtype), None, datt.reshape(-1).to(dtype), dA
+
+
 def segment_mm(bounds, perm, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """out[perm[i]] = a[perm[i]] @ b[r] for the positions i in [bounds[r], bounds[r + 1]) (perm None: identity); rows outside
     [bounds[0], bounds[-1]) are zeros.  One torch.matmul per segment; `b` may be a transposed view."""
