@@ -6,7 +6,8 @@ and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``spars
 ``sparse_bsr_attention`` / ``sparse_ilu0`` / ``sparse_ic0`` / ``sparse_fsai`` / ``sparse_amg`` / ``sparse_coloring`` / ``sparse_sgs`` /
 ``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
 ``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` /
-``sparse_sinkhorn`` / ``sparse_semiring_mm`` / ``sparse_gat_attention`` / ``sparse_gatv2_attention`` beside them;
+``sparse_sinkhorn`` / ``sparse_semiring_mm`` / ``sparse_gat_attention`` / ``sparse_gatv2_attention`` / ``neighbor_mm`` (with
+``voxel_neighbors`` / ``kernel_offsets``) beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -18,6 +19,7 @@ from .sparse_amg import SparseAMG, sparse_amg
 from .sparse_attention import SparseAttention, sparse_attention
 from .sparse_bsr_attention import SparseBSRAttention, sparse_bsr_attention
 from .sparse_bsr_mm import SparseBSRMatMul, sparse_bsr_mm
+from .sparse_conv import NeighborMM, kernel_offsets, neighbor_mm, voxel_neighbors
 from .sparse_coloring import SparseColoredIC0, SparseColoredILU0, SparseColoring, SparseSGS, sparse_coloring, sparse_sgs
 from .sparse_factor import SparseIC0, SparseILU0, sparse_ic0, sparse_ilu0
 from .sparse_fsai import SparseFSAI, sparse_fsai
@@ -101,6 +103,10 @@ __all__ = [
     "sparse_gatv2_attention",
     "SparseGATAttention",
     "SparseGATv2Attention",
+    "neighbor_mm",
+    "voxel_neighbors",
+    "kernel_offsets",
+    "NeighborMM",
     "sparse_attention",
     "SparseGenericLstsq",
     "wait_for_plans",

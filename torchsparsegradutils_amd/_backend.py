@@ -429,6 +429,21 @@ SIGNATURES_GAT = {
 # the header)
 STAGED_GAT = {"tsgu_hip_gat.h": SIGNATURES_GAT}
 
+# the additive entries of csrc/tsgu_hip_conv.h (same library, same ABI version): the thirteenth STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI` and the twelve registries above)
+SIGNATURES_CONV = {
+    "tsgu_neighbor_mm_geometry": (_int, [_int, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                         ctypes.POINTER(_i64)]),
+    "tsgu_neighbor_mm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64,
+                                _int, _ptr]),
+    "tsgu_neighbor_mm_grad_w": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _int,
+                                       _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_conv_cpu.py holds it against
+# the header)
+STAGED_CONV = {"tsgu_hip_conv.h": SIGNATURES_CONV}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -454,7 +469,7 @@ def load_library():
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
                       *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
-                      *STAGED_SEMIRING.values(), *STAGED_GAT.values()):
+                      *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1711,6 +1726,54 @@ def segment_mm_grad_b(plan, a, g, grad_b):
     launch("tsgu_segment_mm_grad_b", dev, vtype_of(a), itype_of(plan.offsets), n, d1, d2, plan.n_seg, plan.offsets, chunk_ptr, part_ptr, chunk,
            max_chunks, plan.perm, a, max(a.stride(0), d1), g, max(g.stride(0), d2), grad_b, ws, nbytes)
     return grad_b
+
+
+def neighbor_mm_geometry(dtype: torch.dtype, n_out: int, k: int, d1: int, d2: int):
+    """(rows of a forward tile, rows of a grad_w chunk, chunks, workspace bytes) of the neighbor_mm kernels: functions of the shapes
+    only.  Host only."""
+    return _query("tsgu_neighbor_mm_geometry", _VTYPE[dtype], int(n_out), int(k), int(d1), int(d2))
+
+
+def _nmm_operands(nbr, x, other, what: str) -> torch.device:
+    dev = require_device(nbr, x, other)
+    if x.dtype != other.dtype:
+        raise RuntimeError(f"{what}: dtypes differ: {x.dtype} and {other.dtype}")
+    if nbr.dim() != 2 or not nbr.is_contiguous() or x.dim() != 2 or (x.stride(1) != 1 and x.size(1) > 1):
+        raise RuntimeError(f"{what}: operands of unexpected layout")
+    return dev
+
+
+def neighbor_mm(nbr, x, w, bias, out):
+    """out[i] = bias + Σ_k x[nbr[i, k]] @ w[k] over the entries of `nbr` (n_out, K; contiguous int32 / int64) inside [0, n_in).
+    `x` and `out` are row-major 2-D; `w` (K, d1, d2) with unit stride on one of its two last axes (a transposed view is read in
+    place); `bias` (d2) contiguous or None."""
+    dev = _nmm_operands(nbr, x, w, "neighbor_mm")
+    require_device(bias, out)
+    n_out, k = nbr.shape
+    n_in, d1 = x.shape
+    d2 = out.size(1)
+    if w.shape != (k, d1, d2) or out.size(0) != n_out or out.dtype != x.dtype or out.stride(1) != 1 or (
+            bias is not None and (bias.dtype != x.dtype or bias.shape != (d2,) or not bias.is_contiguous())):
+        raise RuntimeError("neighbor_mm: operands of unexpected layout")
+    launch("tsgu_neighbor_mm", dev, vtype_of(x), itype_of(nbr), n_in, n_out, k, d1, d2, nbr, x, max(x.stride(0), d1), w, w.stride(0),
+           w.stride(1), w.stride(2), bias, out, max(out.stride(0), d2))
+    return out
+
+
+def neighbor_mm_grad_w(nbr, x, g, grad_w):
+    """grad_w[k] = Σ_i x[nbr[i, k]]ᵀ g[i]; `grad_w` (K, d1, d2) contiguous, `x` and `g` row-major 2-D."""
+    dev = _nmm_operands(nbr, x, g, "neighbor_mm_grad_w")
+    require_device(grad_w)
+    n_out, k = nbr.shape
+    n_in, d1 = x.shape
+    d2 = g.size(1)
+    if g.size(0) != n_out or (g.stride(1) != 1 and d2 > 1) or grad_w.shape != (k, d1, d2) or not grad_w.is_contiguous() or grad_w.dtype != x.dtype:
+        raise RuntimeError("neighbor_mm_grad_w: operands of unexpected layout")
+    nbytes = neighbor_mm_geometry(x.dtype, n_out, k, d1, d2)[3]
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    launch("tsgu_neighbor_mm_grad_w", dev, vtype_of(x), itype_of(nbr), n_in, n_out, k, d1, d2, nbr, x, max(x.stride(0), d1), g,
+           max(g.stride(0), d2), grad_w, ws, nbytes)
+    return grad_w
 
 
 def csr_sptrsm(ptr, idx, val, B, n: int, lower: bool, unit: bool, perm=None, wg_per_cu: int = 1):

@@ -322,6 +322,38 @@ def segment_mm_grad_b(bounds, perm, a: torch.Tensor, g: torch.Tensor, n_seg: int
     return out
 
 
+# ---- neighbor_mm (the torch-op twins of csrc/conv_impl.h) -------------------------------------------------------------------------
+def _neighbor_rows(t: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+    """t[col] with zero rows where col lies outside [0, t.size(0))."""
+    ok = (col >= 0) & (col < t.size(0))
+    return t.index_select(0, col.to(torch.int64).clamp(0, max(t.size(0) - 1, 0))) * ok.to(t.dtype)[:, None]
+
+
+def neighbor_mm(x: torch.Tensor, w: torch.Tensor, nbr: torch.Tensor, bias) -> torch.Tensor:
+    """out[i] = bias + Σ_k x[nbr[i, k]] @ w[k] over the entries of nbr inside [0, n_in); bfloat16 is summed in float32 and rounded
+    once.  `w` may be a transposed view."""
+    _cpu_only(x, w, nbr, bias)
+    acc = torch.float32 if x.dtype == torch.bfloat16 else x.dtype
+    out = torch.zeros((nbr.size(0), w.size(2)), dtype=acc)
+    if x.size(0) > 0:
+        for k in range(nbr.size(1)):
+            out += _neighbor_rows(x, nbr[:, k]).to(acc) @ w[k].to(acc)
+    if bias is not None:
+        out += bias.to(acc)
+    return out.to(x.dtype)
+
+
+def neighbor_mm_grad_w(x: torch.Tensor, g: torch.Tensor, nbr: torch.Tensor) -> torch.Tensor:
+    """grad_w[k] = Σ_i x[nbr[i, k]]ᵀ g[i]."""
+    _cpu_only(x, g, nbr)
+    acc = torch.float32 if x.dtype == torch.bfloat16 else x.dtype
+    out = torch.zeros((nbr.size(1), x.size(1), g.size(1)), dtype=acc)
+    if x.size(0) > 0:
+        for k in range(nbr.size(1)):
+            out[k] = _neighbor_rows(x, nbr[:, k]).to(acc).t() @ g.to(acc)
+    return out.to(x.dtype)
+
+
 # ---- density reductions of the sparse multivariate normal (the torch-op twins of csrc/mvn.hip) ------------------------------------
 def csr_diag_positions(crow: torch.Tensor, col: torch.Tensor, perm, n_rows: int) -> torch.Tensor:
     """pos[i] = position in the owner's value array of the first entry of row i with col == i, -1 when the row stores none."""

@@ -122,7 +122,9 @@ def _evict(key) -> None:
         _PLANS.pop(key, None)
 
 
-def _cached_plan(kind: str, idx: torch.Tensor, n: int, n_seg: int, dev: torch.device, build) -> _Plan:
+def _cached_plan(kind: str, idx: torch.Tensor, n: int, n_seg: int, dev: torch.device, build, what: Optional[str] = None):
+    """The plan of index tensor `idx`, built once per (storage, view, version); its error word `bad` is reported under `what`
+    (sparse_conv.py caches its plans here too, under a kind and a message of its own)."""
     key = _key(kind, idx, n, n_seg, dev)
     with _PLANS_LOCK:
         plan = _PLANS.get(key)
@@ -131,8 +133,9 @@ def _cached_plan(kind: str, idx: torch.Tensor, n: int, n_seg: int, dev: torch.de
             return plan
     plan = build()
     STATS["built"] += 1
-    what = ("gather_mm (idx_b holds indices outside [0, R))" if kind == "gather"
-            else "segment_mm (seglen_a holds negative lengths)")
+    if what is None:
+        what = ("gather_mm (idx_b holds indices outside [0, R))" if kind == "gather"
+                else "segment_mm (seglen_a holds negative lengths)")
     _be._defer_error_check(plan.bad, plan.bad.device, what, status=_ERR_BAD_ARG)   # (sync mode: a bad plan is not cached)
     with _PLANS_LOCK:
         _PLANS[key] = plan
