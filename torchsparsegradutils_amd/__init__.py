@@ -7,7 +7,7 @@ and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``spars
 ``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
 ``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` /
 ``sparse_sinkhorn`` / ``sparse_semiring_mm`` / ``sparse_gat_attention`` / ``sparse_gatv2_attention`` / ``neighbor_mm`` (with
-``voxel_neighbors`` / ``kernel_offsets``) beside them;
+``voxel_neighbors`` / ``kernel_offsets``) / ``sparse_selected_inverse`` (with ``cholesky_pattern``) beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -30,6 +30,7 @@ from .sparse_gat import SparseGATAttention, SparseGATv2Attention, sparse_gat_att
 from .sparse_lstsq import SparseGenericLstsq, sparse_generic_lstsq
 from .sparse_matmul import SparseMatMul, sparse_mm
 from .sparse_mm_reduce import SparseMMReduce, sparse_mm_reduce
+from .sparse_selinv import SparseSelectedInverse, cholesky_pattern, sparse_selected_inverse
 from .sparse_semiring import SparseSemiringMM, sparse_semiring_mm
 from .sparse_sinkhorn import SparseSinkhorn, sparse_sinkhorn
 from .sparse_softmax import SparseSoftmax, sparse_log_softmax, sparse_softmax
@@ -107,6 +108,9 @@ __all__ = [
     "voxel_neighbors",
     "kernel_offsets",
     "NeighborMM",
+    "sparse_selected_inverse",
+    "cholesky_pattern",
+    "SparseSelectedInverse",
     "sparse_attention",
     "SparseGenericLstsq",
     "wait_for_plans",

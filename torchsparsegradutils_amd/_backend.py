@@ -444,6 +444,18 @@ SIGNATURES_CONV = {
 # the header)
 STAGED_CONV = {"tsgu_hip_conv.h": SIGNATURES_CONV}
 
+# the additive entries of csrc/tsgu_hip_selinv.h (same library, same ABI version): the fourteenth STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI` and the thirteen registries above)
+SIGNATURES_SELINV = {
+    "tsgu_csc_selinv_work_bytes": (_i64, [_int, _i64, _i64]),
+    "tsgu_csc_selinv_geometry": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csc_selinv": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_selinv_cpu.py holds it
+# against the header)
+STAGED_SELINV = {"tsgu_hip_selinv.h": SIGNATURES_SELINV}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -469,7 +481,7 @@ def load_library():
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
                       *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
-                      *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values()):
+                      *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values(), *STAGED_SELINV.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1867,6 +1879,46 @@ def csr_factor(kind: str, ptr, idx, diag_pos, val, n: int, shift: float = 0.0, w
            int(wg_per_cu))
     _defer_error_check(work[0:4].view(torch.int32), dev, f"tsgu_csr_{kind} (dependency wait)")
     return out, info
+
+
+def selinv_geometry(dtype: torch.dtype):
+    """(column_capacity, waves_per_block) of the selected inversion for `dtype`: the sub-diagonal entries of a column that are staged
+    in LDS (a longer column is built in the work buffer itself) and the columns a workgroup has in flight."""
+    return _query("tsgu_csc_selinv_geometry", _VTYPE[dtype])
+
+
+def csc_selinv(colptr, rowidx, perm, diag_pos, val, n: int, D=None, wg_per_cu: int = 1):
+    """The entries of (L·Lᵀ)⁻¹ (``D`` None; `diag_pos` the CSC position of every column's diagonal) or ((L+I)·D·(L+I)ᵀ)⁻¹ (L strictly
+    lower, `diag_pos` None) at the stored positions of L, given by its columns (csrc/tsgu_hip_selinv.h): `perm` the position of
+    every CSC entry in `val`.  Ascending unique rows, nothing above the diagonal — the caller's plan has checked that.  Returns
+    (out, diag, info): `out` in the order of `val`, `diag` the diagonal of the inverse (None without ``D``), `info` two device int64
+    (1 + the lowest column with a zero / non-finite pivot, 1 + the lowest column with a lookup that missed).  Nothing is read back here
+    but the error word of the bounded waits, by the protocol of `csr_sptrsm`."""
+    if val.dtype not in FACTOR_DTYPES:
+        raise TypeError(f"tsgu_csc_selinv: float32 and float64 values only, got {val.dtype}")
+    lib = load_library()
+    dev = require_device(colptr, rowidx, perm, diag_pos, val, D)
+    nnz = rowidx.numel()
+    index_arrays = [t for t in (colptr, rowidx, perm, diag_pos) if t is not None]
+    if (colptr.numel() != n + 1 or val.numel() != nnz or (perm is not None and perm.numel() != nnz) or (D is None) == (diag_pos is None)
+            or (diag_pos is not None and diag_pos.numel() != n) or (D is not None and (D.numel() != n or D.dtype != val.dtype))
+            or any(t.dtype != colptr.dtype for t in index_arrays)):
+        raise RuntimeError(f"tsgu_csc_selinv: {n} columns need a column pointer of {n + 1} words, as many values and positions as rows, "
+                           "either diagonal positions or a diagonal D of the value type, and index arrays of one dtype")
+    colptr, rowidx, val = colptr.contiguous(), rowidx.contiguous(), val.contiguous()
+    perm = None if perm is None else perm.contiguous()
+    diag_pos = None if diag_pos is None else diag_pos.contiguous()
+    D = None if D is None else D.contiguous()
+    out = torch.empty_like(val)
+    diag = None if D is None else torch.empty_like(D)
+    info = torch.zeros((2,), dtype=torch.int64, device=dev)
+    if n == 0:
+        return out, diag, info
+    work = torch.empty((lib.tsgu_csc_selinv_work_bytes(vtype_of(val), n, nnz),), dtype=torch.uint8, device=dev)
+    launch("tsgu_csc_selinv", dev, vtype_of(val), itype_of(colptr), n, nnz, colptr, rowidx, perm, diag_pos, val, D, out, diag, work, info,
+           int(wg_per_cu))
+    _defer_error_check(work[0:4].view(torch.int32), dev, "tsgu_csc_selinv (dependency wait)")
+    return out, diag, info
 
 
 def fsai_geometry(dtype: torch.dtype):

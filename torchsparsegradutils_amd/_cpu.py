@@ -690,6 +690,58 @@ def csr_factor(kind: str, crow: torch.Tensor, col: torch.Tensor, diag_pos: torch
     return torch.from_numpy(out), torch.tensor(bad, dtype=torch.int64)
 
 
+def selected_inverse(colptr: torch.Tensor, rowidx: torch.Tensor, perm: torch.Tensor, diag_pos, val: torch.Tensor, n: int, D=None):
+    """The Takahashi recurrence of csrc/tsgu_hip_selinv.h on the CSC view (colptr, rowidx, perm) of a lower factor, column by column
+    from the right in the value type: targets in descending order, a lookup that misses contributes a zero, a zero or non-finite
+    pivot is carried through with IEEE arithmetic.  Reference speed only — one numpy step per stored sub-diagonal entry.  Returns
+    (out, diag, info) like `_backend.csc_selinv`."""
+    import numpy as np
+
+    _cpu_only(colptr, rowidx, perm, diag_pos, val, D)
+    ptr, idx, pm = (t.numpy().astype(np.int64) for t in (colptr, rowidx, perm))
+    lv = val.detach().numpy()[pm]                          # L's values in CSC order
+    dt = lv.dtype.type
+    ldlt = D is not None
+    piv = D.detach().numpy() if ldlt else None
+    sig = np.zeros_like(lv)                                # Σ in CSC order
+    dsig = np.zeros(n, dtype=lv.dtype)
+    first = ptr[:-1] if ldlt else diag_pos.numpy().astype(np.int64) + 1     # the first sub-diagonal position of every column
+    bad = opened = 0
+    with np.errstate(all="ignore"):
+        for i in range(n - 1, -1, -1):
+            p0, e = first[i], ptr[i + 1]
+            s, l = idx[p0:e], lv[p0:e]
+            m = e - p0
+            acc = np.zeros(m, dtype=lv.dtype)
+            for a in range(m - 1, -1, -1):
+                k = s[a]
+                rows_k, sig_k = idx[first[k]:ptr[k + 1]], sig[first[k]:ptr[k + 1]]
+                want = s[a + 1:]
+                x = np.zeros(want.size, dtype=lv.dtype)
+                hit = np.zeros(want.size, dtype=bool)
+                if rows_k.size and want.size:
+                    pos = np.minimum(np.searchsorted(rows_k, want), rows_k.size - 1)
+                    hit = rows_k[pos] == want
+                    x = np.where(hit, sig_k[pos], dt(0))
+                if not hit.all():
+                    opened = i + 1
+                acc[a] = l[a] * dsig[k] + np.sum(l[a + 1:] * x, dtype=lv.dtype)
+                acc[a + 1:] += l[a] * x
+            pivot = piv[i] if ldlt else lv[p0 - 1]
+            if pivot == 0 or not np.isfinite(pivot):
+                bad = i + 1
+            inv = dt(1) / pivot
+            z = -acc if ldlt else -(inv * acc)
+            total = np.sum(l * z, dtype=lv.dtype)
+            dsig[i] = inv - total if ldlt else inv * inv - inv * total
+            sig[p0:e] = z
+            if not ldlt:
+                sig[p0 - 1] = dsig[i]
+    out = np.empty_like(sig)
+    out[pm] = sig
+    return torch.from_numpy(out), (torch.from_numpy(dsig) if ldlt else None), torch.tensor([bad, opened], dtype=torch.int64)
+
+
 def csr_fsai(a_crow: torch.Tensor, a_col: torch.Tensor, a_val: torch.Tensor, s_crow: torch.Tensor, s_col: torch.Tensor, n: int):
     """The FSAI factor G on the lower pattern (s_crow, s_col) for the CSR of tril(A) (include/tsgu_hip_fsai.h has the semantics;
     both patterns with ascending, unique columns and the diagonal last): a plain loop over the rows, one dense Cholesky

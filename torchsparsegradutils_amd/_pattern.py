@@ -1183,6 +1183,69 @@ def factor_plan(g: RowGather) -> FactorPlan:
     return fp
 
 
+# ---- selected inversion (sparse_selinv.py) ------------------------------------------------------------------------------------------
+class SelinvPlan:
+    """What the selected inversion needs of a lower-triangular pattern, cached with it (``selinv_plan``).
+
+    colptr / rowidx   the CSC view of L: ascending, unique rows per column (index dtype of the pattern)
+    perm              position of every CSC entry in L's value array
+    diag_pos          (n,) CSC position of every column's diagonal — its first entry; None for a strictly lower pattern"""
+
+    __slots__ = ("colptr", "rowidx", "perm", "diag_pos")
+
+    def __init__(self, colptr, rowidx, perm, diag_pos):
+        self.colptr, self.rowidx, self.perm, self.diag_pos = colptr, rowidx, perm, diag_pos
+
+
+def selinv_plan(g: RowGather, strict: bool) -> SelinvPlan:
+    """The SelinvPlan of a 2-D square pattern.  Checked once per pattern with one host read: no entry above the diagonal (on it, when
+    `strict`: the LDLᵀ form), no position stored twice and, unless `strict`, a stored diagonal in every column — else ValueError
+    naming the first offending column.  Whether the pattern is closed under elimination is found by the kernel, not here."""
+    key = "selinv_strict" if strict else "selinv"
+    sp = g.core.own.get(key)
+    if sp is not None:
+        if isinstance(sp, ValueError):
+            raise sp
+        return sp
+    if g.batch is not None or g.n_rows != g.n_cols:
+        raise ValueError("selinv_plan: a 2-D square pattern is required")
+    n, dev = g.n_rows, g.col.device
+    t = g.transposed                       # columns of L as groups; rows ascend within a column when they ascend within L's rows
+    rows, cols = t.col.to(torch.int64), t.row_indices().to(torch.int64)
+    big = torch.full((), n, dtype=torch.int64, device=dev)
+    order = rows[1:] - rows[:-1]
+    same = cols[1:] == cols[:-1]
+    upper =torch.where((rows <= cols) if strict else (rows < cols), cols, big).min() if rows.numel() else big
+    if rows.numel() > 1:
+        dup = torch.where(same & (order == 0), cols[1:], big).min()
+        unsorted = torch.where(same & (order < 0), cols[1:], big).min()
+    else:
+        dup = unsorted = big
+    if strict or n == 0:
+        missing = big
+    else:
+        first = t.crow[:-1].to(torch.int64)
+        has = (t.crow[1:].to(torch.int64) > first) & (rows[first.clamp(max=max(rows.numel() - 1, 0))] == torch.arange(n, device=dev))
+        missing = torch.where(has, big, torch.arange(n, device=dev)).min()
+    upper, dup, unsorted, missing = (int(v) for v in torch.stack((upper, dup, unsorted, missing)).tolist())
+    err = None
+    if upper < n:
+        err = ValueError(f"sparse_selected_inverse: column {upper} stores an entry {'on or ' if strict else ''}above the diagonal: L must "
+                         f"be {'strictly ' if strict else ''}lower triangular")
+    elif dup < n or unsorted < n:
+        c = min(dup, unsorted)
+        err = ValueError(f"sparse_selected_inverse: column {c} stores a position more than once or out of order")
+    elif missing < n:
+        err = ValueError(f"sparse_selected_inverse: column {missing} does not store its diagonal")
+    if err is not None:
+        g.core.own[key] = err
+        raise err
+    idt = t.crow.dtype
+    diag_pos = None if strict else t.crow[:-1].to(idt).contiguous()
+    sp = g.core.own[key] = SelinvPlan(t.crow.contiguous(), t.col.to(idt).contiguous(), t.perm.to(idt).contiguous(), diag_pos)
+    return sp
+
+
 # ---- factorised sparse approximate inverse (sparse_fsai.py) ---------------------------------------------------------------------------
 FSAI_CLASSES = (8, 16, 32)      # a row of S of at most 8 / 16 / 32 / more entries is built by 8 / 16 / 32 / 64 lanes (csrc/fsai_impl.h)
 

@@ -409,6 +409,42 @@ class SparseMultivariateNormal(Distribution):
                                       "sparse operation; it is provided for scale_tril only")
         return _variance(factor, diagonal, bool(self._validate_args)).expand(self._batch_shape + self._event_shape)
 
+    def marginal_variance(self, check: bool = True):
+        r"""Diagonal of ``Σ`` for either parameterisation.  For ``precision_tril`` it is the diagonal of the selected inverse
+        (``sparse_selected_inverse``: the Takahashi recurrence on the factor's own pattern, which must be closed under elimination;
+        ``check`` as there), computed under ``no_grad``, a batched factor by one call per item.  For ``scale_tril`` it is
+        :attr:`variance`."""
+        factor, diagonal, covariance = self._parameters()
+        if covariance:
+            return self.variance
+        from ..sparse_selinv import sparse_selected_inverse
+
+        def one(L, D):
+            if D is not None:
+                return sparse_selected_inverse(L, D, check=check)[1]
+            Z = sparse_selected_inverse(L, check=check)
+            if Z.layout == torch.sparse_csr:
+                Z = Z.to_sparse_coo()
+            idx = Z.indices()
+            return torch.zeros(L.size(0), dtype=Z.dtype, device=Z.device).index_add_(0, idx[0], Z.values() * (idx[0] == idx[1]))
+
+        with torch.no_grad():
+            factor = factor.detach()
+            D = None if diagonal is None else diagonal.detach()
+            if factor.dim() == 2:
+                out = one(factor, D)
+            else:
+                items = []
+                for b in range(factor.size(0)):
+                    if factor.layout == torch.sparse_csr:
+                        Lb = torch.sparse_csr_tensor(factor.crow_indices()[b], factor.col_indices()[b], factor.values()[b], factor.shape[1:])
+                    else:
+                        Lb = factor[b].coalesce()
+                    items.append(one(Lb, None if D is None else (D[b] if D.dim() == 2 else D)))
+                out = torch.stack(items)
+        return out.expand(self._batch_shape + self._event_shape)
+
+
 class SparseMultivariateNormalNative(Distribution):
     r"""The reference's second sparse multivariate normal (``sparse_multivariate_normal.py:392-589``): ``Σ = L Lᵀ`` with an
     unbatched CSR factor ``L`` (stored positive diagonal) and ``loc`` of shape ``(n,)``.  Same constructor checks and messages.
