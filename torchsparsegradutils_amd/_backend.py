@@ -456,6 +456,22 @@ SIGNATURES_SELINV = {
 # against the header)
 STAGED_SELINV = {"tsgu_hip_selinv.h": SIGNATURES_SELINV}
 
+# the additive entries of csrc/tsgu_hip_lsmr.h (same library, same ABI version): the fifteenth STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI` and the fourteen registries above)
+SIGNATURES_LSMR = {
+    "tsgu_lsmr_scal_rows": (_int, []),
+    "tsgu_lsmr_scalar": (_int, [_int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _int, _ptr]),
+    "tsgu_lsmr_vector": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_lsmr_cpu.py holds it against the
+# header)
+STAGED_LSMR = {"tsgu_hip_lsmr.h": SIGNATURES_LSMR}
+
+# rows of the LSMR scalar block (csrc/tsgu_hip_lsmr.h) that utils/lsmr.py fills before the first step
+LSMR_ROW = {"alpha": 0, "beta": 1, "alphabar": 2, "rho": 3, "rhobar": 4, "cbar": 5, "zetabar": 8, "betadd": 9, "rhodold": 11,
+            "norm_a2": 15, "minrbar": 17, "normb": 18, "s_prod": 22, "s_self": 23}
+
 
 class HipExtensionMissing(RuntimeError):
     pass
@@ -481,7 +497,8 @@ def load_library():
         for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
                       *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
-                      *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values(), *STAGED_SELINV.values()):
+                      *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values(), *STAGED_SELINV.values(),
+                      *STAGED_LSMR.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res

@@ -4,11 +4,17 @@ Comput. 33(5), 2011: Golub–Kahan bidiagonalisation + two QR sweeps; the refere
 Same signature and stopping rules (``atol`` / ``btol`` / ``conlim`` tests of the paper, §6; reference :339-383).  What
 differs is where the work happens: the two products per iteration, ``A·v`` and ``Aᵀ·u``, run on the K1 HIP kernel
 (``Aᵀ`` through the cached transposed pattern — the reference converts CSC→CSR inside ATen at every call), the vector
-recurrences are device tensor ops, and all right-hand sides advance in LOCK-STEP: the reference's default least-squares
-solver loops over the columns in Python (sparse_lstsq.py:124-147), here a column that has met its stopping test is
-frozen while the others continue.  The O(1)-per-column scalars (rotations, norm estimates) live on the host in
-float64; two small device→host reads per iteration (the norms β, α) replace the reference's two syncs
-(``beta > 0`` and ``if stop``, :272, :381).
+recurrences run on the fused K8 kernels (``csrc/lsmr.hip``), and all right-hand sides advance in LOCK-STEP: the
+reference's default least-squares solver loops over the columns in Python (sparse_lstsq.py:124-147), here a column that
+has met its stopping test is frozen while the others continue.
+
+Fused path (``ENABLE_FUSED``; ``b`` on the GPU, float32 / float64, a width the Krylov step kernels take): the Golub–Kahan
+vectors are kept unnormalised with their norms on the device, so one iteration is two products, three streaming passes
+(two half steps of the bidiagonalisation, one update of h̄, x and h) and three single-workgroup launches for the
+rotations, estimates and stopping tests, whose O(1)-per-column scalars live on the device in float64.  The host reads one
+stop word every 10 iterations; with the package's own sparse products a long solve replays the 10 iterations as a
+hipGraph.  Anything else runs the host-driven loop below it: tensor ops around the two products, the scalars in numpy
+float64, three small device→host reads per iteration (the norms β, α, ‖x‖).
 """
 
 from __future__ import annotations
@@ -19,7 +25,11 @@ import numpy as np
 import torch
 
 from .. import _backend as _be
-from ._operator import SparseOperator
+from . import _graph
+from ._operator import LAST_SOLVE, SparseOperator, checked, record_solve
+
+ENABLE_FUSED = True  # False: the host-driven loop (tensor ops around the two products, scalars in numpy; tests compare the two)
+_POLL = 10           # iterations between two reads of the stop word
 
 
 def _rotation(a: np.ndarray, b: np.ndarray):
@@ -42,6 +52,7 @@ def _transposed_operator(A: torch.Tensor):
             return _ops.spmm(plan_t, op.values, u.unsqueeze(-1)).squeeze(-1)
         return _ops.spmm(plan_t, op.values, u)
 
+    rmatvec.own = True  # a product of this package: may be recorded into a graph
     return op, rmatvec
 
 
@@ -103,6 +114,8 @@ def lsmr(
     signature parity (the β > 0 test costs nothing here: β is needed on the host anyway)."""
     user_mat, user_rmat = callable(A) and not torch.is_tensor(A), callable(Armat) and not torch.is_tensor(Armat)
     mat, rmat, n = _as_pair(A, Armat, n)
+    # only the package's own sparse products are recorded into a graph: other closures and dense operators are opaque
+    own = all(isinstance(f, SparseOperator) or getattr(f, "own", False) for f in (mat, rmat))
     if torch.atleast_1d(b).dim() == 1:
         # user closures see the 1-D vectors the reference hands them; the kernels work on (·, 1) columns
         if user_mat:
@@ -120,6 +133,11 @@ def lsmr(
     ctol = 1.0 / conlim if conlim > 0 else 0.0
     if maxiter is None:
         maxiter = min(m, n)
+
+    if ENABLE_FUSED and B.is_cuda and k >= 1 and m > 0 and n > 0 and _be.load_library().tsgu_cg_num_blocks(_be.vtype_of(B), m, k) >= 0:
+        x, its, reached = _lsmr_fused(mat, rmat, B, x0, n, float(damp), float(atol), float(btol), ctol, eps, int(maxiter), own)
+        record_solve(solver="lsmr", fused=True, iterations=int(its.max()), column_iterations=its, tolerance_reached=reached)
+        return (x[:, 0] if vector else x), int(its.max())
 
     def row(a: np.ndarray) -> torch.Tensor:  # per-column coefficients as a (1, k) device tensor
         return torch.as_tensor(a, dtype=dt, device=dev).unsqueeze(0)
@@ -241,4 +259,76 @@ def lsmr(
         done = done | stop
 
     out = x[:, 0] if vector else x
+    record_solve(solver="lsmr", fused=False, iterations=int(its.max()) if k else 0, column_iterations=its,
+                 tolerance_reached=bool(done.all()))
     return out, int(its.max()) if k else 0
+
+
+def _lsmr_fused(mat, rmat, B: torch.Tensor, x0, n: int, damp: float, atol: float, btol: float, ctol: float, eps: float,
+                maxiter: int, own: bool):
+    """LSMR on the K8 kernels (csrc/lsmr.hip) for the (m, p) right-hand sides `B`: returns (x, per-column iteration counts,
+    every column met a stopping test).  u~ = β u and v~ = α v are kept unnormalised; scalars and flags as csrc/tsgu_hip_lsmr.h
+    lays them out."""
+    lib = _be.load_library()
+    m, p = B.shape
+    dt, dev, vt = B.dtype, B.device, _be.vtype_of(B)
+    nb_m, nb_n = _be.krylov_num_blocks("lsmr", B, m, p), _be.krylov_num_blocks("lsmr", B, n, p)
+
+    def product(f, w):  # 16-byte aligned, contiguous, of the working dtype: what the step kernels take
+        out = checked(f(w), dt).contiguous()
+        return out if out.data_ptr() % 16 == 0 else out.clone()
+
+    def colnorm(w):
+        return _be.coldot(w, w).double().clamp_min(0).sqrt()
+
+    # set-up (tensor ops, no host read): x0, β₁ u₁ = b − A x₀, α₁ v₁ = Aᵀ u₁, solved columns, zero b
+    normb = colnorm(B)
+    if x0 is None:
+        x = torch.zeros((n, p), dtype=dt, device=dev)
+        u, beta = B.clone(), normb
+    else:
+        x = (torch.atleast_1d(x0).reshape(n, -1).to(dt) * (normb > 0).to(dt)).contiguous()   # b = 0: x = 0 (reference :237-243)
+        u = (B - product(mat, x)).contiguous()
+        beta = colnorm(u)
+    one = torch.ones_like(beta)
+    v = (product(rmat, u) * torch.where(beta > 0, 1.0 / torch.where(beta > 0, beta, one), 0.0).to(dt)).contiguous()   # v~ = α v
+    alpha = colnorm(v)
+    h = (v / torch.where(alpha > 0, alpha, one).to(dt)).contiguous()
+    hbar = torch.zeros_like(v)
+
+    R = _be.LSMR_ROW
+    scal = torch.zeros((lib.tsgu_lsmr_scal_rows(), p), dtype=torch.float64, device=dev)
+    scal[R["alpha"]], scal[R["beta"]], scal[R["alphabar"]], scal[R["normb"]] = alpha, beta, alpha, normb
+    scal[R["rho"]] = scal[R["rhobar"]] = scal[R["cbar"]] = scal[R["rhodold"]] = 1
+    scal[R["zetabar"]], scal[R["betadd"]], scal[R["norm_a2"]] = alpha * beta, beta, alpha ** 2
+    scal[R["minrbar"]] = 0.99 * float(torch.finfo(dt).max)
+    scal[R["s_prod"]] = torch.where(alpha > 0, 1.0 / torch.where(alpha > 0, alpha, one), 0.0)
+    scal[R["s_self"]] = torch.where(beta > 0, alpha / torch.where(beta > 0, beta, one), 0.0)
+    done0 = (alpha * beta == 0) | (normb == 0)
+    flags = torch.zeros(2 + 2 * p, dtype=torch.int32, device=dev)
+    flags[2:2 + p] = done0
+    flags[0] = done0.all()
+    part = torch.empty((max(nb_m, nb_n), p), dtype=dt, device=dev)
+    fold = torch.empty((lib.tsgu_cg_fold_rows(), p), dtype=dt, device=dev)
+
+    def scalar(phase, rows):
+        _be.launch("tsgu_lsmr_scalar", dev, vt, phase, part, rows, fold, scal, flags, damp, atol, btol, ctol, eps, p)
+
+    def iteration(_):
+        _be.launch("tsgu_lsmr_vector", dev, vt, 0, m, p, u, product(mat, v), None, None, scal, flags, part)     # β u = A v − α u
+        scalar(0, nb_m)
+        _be.launch("tsgu_lsmr_vector", dev, vt, 0, n, p, v, product(rmat, u), None, None, scal, flags, part)    # α v = Aᵀ u − β v
+        scalar(1, nb_n)
+        _be.launch("tsgu_lsmr_vector", dev, vt, 1, n, p, x, v, h, hbar, scal, flags, part)                     # h̄, x, h; ‖x‖
+        scalar(2, nb_n)
+
+    with torch.cuda.device(dev):
+        _graph.run_chunked(iteration, lambda: bool(flags[0].item()), _POLL, bound=maxiter, capturable=own and _graph.enabled())
+        words = flags.tolist()                                       # the one read after the loop
+    return x, np.asarray(words[2 + p:], dtype=np.int64), all(words[2:2 + p])
+
+
+def last_solve_info():
+    """Diagnostics of this thread's most recent ``lsmr`` call (largest and per-column iteration counts, whether every column met
+    a stopping test, which path ran)."""
+    return LAST_SOLVE.info.get("lsmr")
