@@ -7,7 +7,8 @@ and ``sparse_softmax`` / ``sparse_log_softmax`` / ``sparse_attention`` / ``spars
 ``sparse_lobpcg`` / ``sparse_logdet`` / ``sparse_inv_quad_logdet`` / ``sparse_inv_sqrt_mm`` / ``sparse_sqrt_mm`` / ``sparse_expm_mm`` /
 ``sparse_topk_mm`` / ``sparse_semi_structured_mm`` / ``sparse_semi_structured_linear`` / ``sparse_semi_structured_prune`` /
 ``sparse_sinkhorn`` / ``sparse_semiring_mm`` / ``sparse_gat_attention`` / ``sparse_gatv2_attention`` / ``neighbor_mm`` (with
-``voxel_neighbors`` / ``kernel_offsets``) / ``sparse_selected_inverse`` (with ``cholesky_pattern``) beside them;
+``voxel_neighbors`` / ``kernel_offsets``) / ``sparse_selected_inverse`` (with ``cholesky_pattern``) /
+``sparse_banded_triangular_solve`` beside them;
 the arithmetic runs in hand-written HIP kernels behind the C ABI in ``include/tsgu_hip.h``.  GPU only — there is no CPU fallback.
 """
 
@@ -17,6 +18,7 @@ from ._pattern import wait_for_plans
 from .indexed_matmul import GatherMM, SegmentMM, gather_mm, segment_mm
 from .sparse_amg import SparseAMG, sparse_amg
 from .sparse_attention import SparseAttention, sparse_attention
+from .sparse_banded_solve import SparseBandedTriangularSolve, sparse_banded_triangular_solve
 from .sparse_bsr_attention import SparseBSRAttention, sparse_bsr_attention
 from .sparse_bsr_mm import SparseBSRMatMul, sparse_bsr_mm
 from .sparse_conv import NeighborMM, kernel_offsets, neighbor_mm, voxel_neighbors
@@ -111,6 +113,8 @@ __all__ = [
     "sparse_selected_inverse",
     "cholesky_pattern",
     "SparseSelectedInverse",
+    "sparse_banded_triangular_solve",
+    "SparseBandedTriangularSolve",
     "sparse_attention",
     "SparseGenericLstsq",
     "wait_for_plans",

@@ -468,6 +468,19 @@ SIGNATURES_LSMR = {
 # header)
 STAGED_LSMR = {"tsgu_hip_lsmr.h": SIGNATURES_LSMR}
 
+# the additive entries of csrc/tsgu_hip_band.h (same library, same ABI version): the sixteenth STAGED header, in a registry of its
+# own for the same reason (tests pin `ABI` and the fifteen registries above)
+SIGNATURES_BAND = {
+    "tsgu_csr_band_geometry": (_int, [_int, _i64, _i64, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_band_sptrsm_work_bytes": (_i64, [_int, _i64, _i64, _int, _int, _int]),
+    "tsgu_csr_band_sptrsm": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr, _i64, _i64, _ptr, _int,
+                                    _int, _int, _ptr]),
+}
+
+# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_banded_cpu.py holds it
+# against the header)
+STAGED_BAND = {"tsgu_hip_band.h": SIGNATURES_BAND}
+
 # rows of the LSMR scalar block (csrc/tsgu_hip_lsmr.h) that utils/lsmr.py fills before the first step
 LSMR_ROW = {"alpha": 0, "beta": 1, "alphabar": 2, "rho": 3, "rhobar": 4, "cbar": 5, "zetabar": 8, "betadd": 9, "rhodold": 11,
             "norm_a2": 15, "minrbar": 17, "normb": 18, "s_prod": 22, "s_self": 23}
@@ -498,7 +511,7 @@ def load_library():
                       *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
                       *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
                       *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values(), *STAGED_SELINV.values(),
-                      *STAGED_LSMR.values()):
+                      *STAGED_LSMR.values(), *STAGED_BAND.values()):
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1856,6 +1869,44 @@ def csr_sptrsm_lattice(tables, val, B, n: int, lower: bool, unit: bool, workgrou
     launch("tsgu_csr_sptrsm_lattice", dev, vtype_of(val), tables.struct_addr, val.numel(), val, int(bool(lower)), int(bool(unit)), B, ldb, b_cs,
            X, _ld(X), p, work, int(workgroups))
     _defer_error_check(work[512:516].view(torch.int32), dev, "tsgu_csr_sptrsm_lattice (dependency wait)")
+    return X
+
+
+BAND_MAX_WIDTH = 8
+
+
+def band_geometry(dtype: torch.dtype, n: int, p: int, w: int, chunk_rows=None, group_chunks=None):
+    """(rows of a chunk, chunk summaries of a carry group, longest chain one workgroup walks) of the banded solve: pure functions of
+    (n, p, w, dtype) and the two overrides (csrc/tsgu_hip_band.h)."""
+    return _query("tsgu_csr_band_geometry", _VTYPE[dtype], int(n), int(p), int(w), int(chunk_rows or 0), int(group_chunks or 0))
+
+
+def csr_band_sptrsm(crow, col, values, rhs, n: int, w: int, lower: bool, unit: bool, transpose: bool, chunk_rows=None, group_chunks=None):
+    """X = op(A)⁻¹ rhs for the CSR arrays of a matrix whose selected triangle (`lower`: of A itself) lies within `w` <= 8 of the
+    diagonal, by the three-phase log-depth solve of csrc/band_impl.h: chunk reduce, carry, chunk apply — plain launches, no waits
+    between workgroups, no error word, safe under graph capture.  Columns strictly ascending per row (the caller's plan has
+    checked that and `w`).  `chunk_rows` / `group_chunks` override the geometry (tests: every carry level at a small n)."""
+    if values.dtype not in FACTOR_DTYPES:
+        raise TypeError(f"tsgu_csr_band_sptrsm: float32 and float64 values only, got {values.dtype}")
+    lib = load_library()
+    dev = require_device(crow, col, values, rhs)
+    if values.dtype != rhs.dtype:
+        raise RuntimeError(f"expected A and B to have the same dtype, got {values.dtype} and {rhs.dtype}")
+    if rhs.dim() != 2 or rhs.size(0) != n or crow.numel() != n + 1 or col.numel() != values.numel() or crow.dtype != col.dtype:
+        raise RuntimeError(f"tsgu_csr_band_sptrsm: a system of {n} rows needs a right-hand side of {n} rows, a row pointer of {n + 1} "
+                           f"words and as many values as columns, got {tuple(rhs.shape)}, {crow.numel()}, {values.numel()} / {col.numel()}")
+    if not 0 <= w <= BAND_MAX_WIDTH:
+        raise ValueError(f"tsgu_csr_band_sptrsm: band width {w} outside 0 … {BAND_MAX_WIDTH}")
+    rhs = rowmajor(rhs)
+    p = rhs.size(-1)
+    crow, col, values = crow.contiguous(), col.contiguous(), values.contiguous()
+    X = torch.empty((n, p), dtype=rhs.dtype, device=dev)
+    if n == 0 or p == 0:
+        return X
+    cr, gc = int(chunk_rows or 0), int(group_chunks or 0)
+    work = torch.empty((lib.tsgu_csr_band_sptrsm_work_bytes(vtype_of(values), n, p, w, cr, gc),), dtype=torch.uint8, device=dev)
+    launch("tsgu_csr_band_sptrsm", dev, vtype_of(values), itype_of(crow), n, col.numel(), crow, col, values, int(w), int(bool(lower)),
+           int(bool(unit)), int(bool(transpose)), rhs, _ld(rhs), X, _ld(X), p, work, cr, gc)
     return X
 
 

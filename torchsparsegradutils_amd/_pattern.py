@@ -1246,6 +1246,41 @@ def selinv_plan(g: RowGather, strict: bool) -> SelinvPlan:
     return sp
 
 
+# ---- banded triangular solves (sparse_banded_solve.py) ------------------------------------------------------------------------------
+class BandPlan:
+    """What the banded solve needs of a 2-D pattern, cached with it (``band_plan``): ``width``, the largest |row − col| on the
+    selected side of the diagonal.  The solve reads the pattern's own arrays in all four modes: nothing else is built."""
+
+    __slots__ = ("width",)
+
+    def __init__(self, width: int):
+        self.width = width
+
+
+def band_plan(g: RowGather, lower: bool) -> BandPlan:
+    """The BandPlan of the `lower` (else upper) triangle of a 2-D pattern: one device pass over the index tensors (both widths and the
+    ascending-columns check) and one host read per pattern.  ValueError when a row's columns are not strictly ascending."""
+    got = g.core.own.get("band")
+    if got is None:
+        if g.batch is not None:
+            raise ValueError("band_plan: a 2-D pattern is required (flatten a batched one first)")
+        rows, cols = g.row_indices().to(torch.int64), g.col.to(torch.int64)
+        zero = torch.zeros((), dtype=torch.int64, device=cols.device)
+        d = rows - cols
+        below = d.max().clamp(min=0) if d.numel() else zero
+        above = (-d).max().clamp(min=0) if d.numel() else zero
+        if d.numel() > 1:
+            unsorted = ((rows[1:] == rows[:-1]) & (cols[1:] <= cols[:-1])).any().to(torch.int64)
+        else:
+            unsorted = zero
+        below, above, unsorted = (int(v) for v in torch.stack((below, above, unsorted)).tolist())
+        got = g.core.own["band"] = (ValueError("sparse_banded_triangular_solve: the columns of every row must be strictly ascending")
+                                    if unsorted else (BandPlan(below), BandPlan(above)))
+    if isinstance(got, ValueError):
+        raise got
+    return got[0 if lower else 1]
+
+
 # ---- factorised sparse approximate inverse (sparse_fsai.py) ---------------------------------------------------------------------------
 FSAI_CLASSES = (8, 16, 32)      # a row of S of at most 8 / 16 / 32 / more entries is built by 8 / 16 / 32 / 64 lanes (csrc/fsai_impl.h)
 
