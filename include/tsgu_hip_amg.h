@@ -1,8 +1,7 @@
 /*
  * tsgu_hip_amg.h — the kernels of the aggregation multigrid preconditioner (sparse_amg): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_AMG`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` + `stream`
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` + `stream`
  * last, status codes, tsgu_vtype / tsgu_itype, no synchronisation, no allocation).  The entries are additive, so TSGU_ABI_VERSION
  * stays as it is.  The reference has no counterpart.
  *
@@ -22,7 +21,7 @@
 #ifndef TSGU_HIP_AMG_H
 #define TSGU_HIP_AMG_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

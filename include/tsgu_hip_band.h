@@ -2,8 +2,7 @@
  * tsgu_hip_band.h — triangular solves with a BANDED factor in logarithmic depth (sparse_banded_solve.py): entries of
  * libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_BAND`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
  * `stream` last, status codes, tsgu_vtype / tsgu_itype, no synchronisation, no allocation).  The entries are additive, so
  * TSGU_ABI_VERSION stays as it is.  The reference has no counterpart.
  *
@@ -15,7 +14,7 @@
 #ifndef TSGU_HIP_BAND_H
 #define TSGU_HIP_BAND_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

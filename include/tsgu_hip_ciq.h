@@ -2,8 +2,7 @@
  * tsgu_hip_ciq.h — the contour-quadrature update of sparse_inv_sqrt_mm / sparse_sqrt_mm (sparse_sqrt.py): entries of
  * libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_CIQ`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
  * `stream` last, status codes, tsgu_vtype, no synchronisation, no allocation, no atomics on values).  The entries are additive, so
  * TSGU_ABI_VERSION stays as it is.  The reference has no counterpart: it copied multi-shift MINRES and dropped the caller.
  *
@@ -24,7 +23,7 @@
 #ifndef TSGU_HIP_CIQ_H
 #define TSGU_HIP_CIQ_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

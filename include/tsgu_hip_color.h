@@ -2,8 +2,7 @@
  * tsgu_hip_color.h — the kernels of the multicolour ordering (sparse_coloring, and the coloured forms of sparse_ilu0, sparse_ic0 and
  * sparse_sgs): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_COLOR`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` + `stream`
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` + `stream`
  * last, status codes, tsgu_vtype / tsgu_itype, no synchronisation, no allocation).  The entries are additive, so TSGU_ABI_VERSION
  * stays as it is.  The reference has no counterpart.
  *
@@ -26,7 +25,7 @@
 #ifndef TSGU_HIP_COLOR_H
 #define TSGU_HIP_COLOR_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

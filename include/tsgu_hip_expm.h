@@ -1,8 +1,7 @@
 /*
  * tsgu_hip_expm.h — the Chebyshev recurrence of sparse_expm_mm (sparse_expm.py): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_EXPM`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
  * `stream` last, status codes, tsgu_vtype, no synchronisation, no allocation, no atomics, no reductions).  The entries are
  * additive, so TSGU_ABI_VERSION stays as it is.  The reference has no counterpart: it has no matrix exponential.
  *
@@ -24,7 +23,7 @@
 #ifndef TSGU_HIP_EXPM_H
 #define TSGU_HIP_EXPM_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

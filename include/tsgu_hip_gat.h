@@ -1,8 +1,7 @@
 /*
  * tsgu_hip_gat.h — fused graph-attention layers over a sparse pattern (sparse_gat.py): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_GAT`.  An addition to the C ABI of tsgu_hip.h with the conventions stated in tsgu_hip_semiring.h (device
+ * An addition to the C ABI of tsgu_hip.h with the conventions stated in tsgu_hip_semiring.h (device
  * pointers, leading dimensions in elements, `device` + `stream` last, status codes, tsgu_vtype / tsgu_itype, no synchronisation, no
  * allocation, no global atomics, graph-capturable).  The entries are additive, so TSGU_ABI_VERSION stays as it is.  The reference
  * has no counterpart.
@@ -30,7 +29,7 @@
 #ifndef TSGU_HIP_GAT_H
 #define TSGU_HIP_GAT_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -2,8 +2,7 @@
  * tsgu_hip_lsmr.h — the step kernels of LSMR (utils/lsmr.py; Fong & Saunders, SIAM J. Sci. Comput. 33(5), 2011): entries of
  * libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_LSMR`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` + `stream`
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` + `stream`
  * last, status codes, tsgu_vtype, no synchronisation, no allocation).  The entries are additive, so TSGU_ABI_VERSION stays as it
  * is.
  *
@@ -36,7 +35,7 @@
 #ifndef TSGU_HIP_LSMR_H
 #define TSGU_HIP_LSMR_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -2,8 +2,7 @@
  * tsgu_hip_quadrature.h — Gauss quadrature of Lanczos tridiagonal matrices and the Rademacher probe block of sparse_logdet
  * (sparse_logdet.py): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_QUADRATURE`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
  * `stream` last, status codes, tsgu_vtype, no synchronisation, no allocation).  The entries are additive, so TSGU_ABI_VERSION stays
  * as it is.  The reference has no counterpart: its linear_cg returns the tridiagonal matrices and stops there.
  *
@@ -29,7 +28,7 @@
 #ifndef TSGU_HIP_QUADRATURE_H
 #define TSGU_HIP_QUADRATURE_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -2,8 +2,7 @@
  * tsgu_hip_semi.h — 2:4 semi-structured operands (sparse_semi_structured.py): prune, expand, A·Yᵀ, Aᵀ·G and the SDDMM on the kept
  * positions; entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_SEMI`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
  * `stream` last, status codes, tsgu_vtype, no synchronisation, no allocation, no global atomics).  The entries are additive, so
  * TSGU_ABI_VERSION stays as it is.  The reference has no counterpart.
  *
@@ -28,7 +27,7 @@
 #ifndef TSGU_HIP_SEMI_H
 #define TSGU_HIP_SEMI_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

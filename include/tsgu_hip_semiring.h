@@ -1,8 +1,7 @@
 /*
  * tsgu_hip_semiring.h — sparse × dense products in the log and tropical semirings (sparse_semiring.py): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_SEMIRING`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, leading
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, leading
  * dimensions in elements, `device` + `stream` last, status codes, tsgu_vtype / tsgu_itype, no synchronisation, no allocation, no
  * global atomics).  The entries are additive, so TSGU_ABI_VERSION stays as it is.  The reference has no counterpart.
  *
@@ -33,7 +32,7 @@
 #ifndef TSGU_HIP_SEMIRING_H
 #define TSGU_HIP_SEMIRING_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

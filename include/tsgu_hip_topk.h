@@ -1,8 +1,7 @@
 /*
  * tsgu_hip_topk.h — the k largest of scale·Q·Kᵀ + key_bias per row as CSR arrays (sparse_topk.py): entries of libtsgu_hip.so.
  *
- * STAGED: this header lives beside the sources and not under include/ ("Adding a header"); its entries are bound
- * from `_backend.STAGED_TOPK`.  An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
+ * An addition to the C ABI of tsgu_hip.h with the same conventions (device pointers, `device` +
  * `stream` last, status codes, tsgu_vtype / tsgu_itype, no synchronisation, no allocation, no global atomics).  The entries are
  * additive, so TSGU_ABI_VERSION stays as it is.  The reference has no counterpart.
  *
@@ -15,7 +14,7 @@
 #ifndef TSGU_HIP_TOPK_H
 #define TSGU_HIP_TOPK_H
 
-#include "../../include/tsgu_hip.h"
+#include "tsgu_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,5 +1,5 @@
 """Float64 numpy restatement of the contour-quadrature rule of `sparse_inv_sqrt_mm` and of one `tsgu_ciq_update` / `tsgu_ciq_stop`
-step (csrc/tsgu_hip_ciq.h), with the magnitudes the kernel test's rounding bound is built from.  No torch, no scipy."""
+step (include/tsgu_hip_ciq.h), with the magnitudes the kernel test's rounding bound is built from.  No torch, no scipy."""
 
 import math
 

@@ -1,4 +1,4 @@
-"""Plain numpy reference for the multicolour ordering (csrc/tsgu_hip_color.h, sparse_coloring.py): the sequential greedy colouring,
+"""Plain numpy reference for the multicolour ordering (include/tsgu_hip_color.h, sparse_coloring.py): the sequential greedy colouring,
 the permutation, the per-colour sweeps in float64, and the error bounds of a sweep and of a whole application.  No GPU, no oracle
 binary.  The triangular-solve pieces come from tests/_trsm_ref.py (`solve64`, `bound`, `ratio`, `emulate`), imported as they are.
 

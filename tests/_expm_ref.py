@@ -1,5 +1,5 @@
 """Float64 numpy restatement of `sparse_expm_mm`: the coefficient rule, the dense Chebyshev expansion and its adjoint, one
-`tsgu_cheb_step` / `tsgu_cheb_combine` launch (csrc/tsgu_hip_expm.h) with the magnitudes the kernel test's rounding bound is built
+`tsgu_cheb_step` / `tsgu_cheb_combine` launch (include/tsgu_hip_expm.h) with the magnitudes the kernel test's rounding bound is built
 from, and the test matrices.  No torch, no scipy."""
 
 import math

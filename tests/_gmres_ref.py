@@ -1,4 +1,4 @@
-"""High-precision mirror of the GMRES entry points of csrc/tsgu_hip_gmres.h, the whole solve chained from them, and the two small
+"""High-precision mirror of the GMRES entry points of include/tsgu_hip_gmres.h, the whole solve chained from them, and the two small
 nonsymmetric test matrices.
 
 One function per entry point, written from the contracts in the header — not from the kernels — on `Tr` of _krylov_ref.py: a value

@@ -54,7 +54,7 @@ def _ratio(num, den):
 
 def ref_scalar(phase, sums, scal, flags, damp, atol, btol, ctol, eps):
     """One launch of tsgu_lsmr_scalar in float64 numpy, from the column sums it folds: (scal, flags) after it, as
-    csrc/tsgu_hip_lsmr.h states the phases (the recurrences are those of utils/lsmr.py's host-driven loop)."""
+    include/tsgu_hip_lsmr.h states the phases (the recurrences are those of utils/lsmr.py's host-driven loop)."""
     S, F = scal.copy(), flags.copy()
     p = S.shape[1]
     if F[0]:

@@ -1,4 +1,4 @@
-"""Float64 mirror of the Lanczos quadrature (csrc/tsgu_hip_quadrature.h) and the test matrices of sparse_logdet, in numpy.
+"""Float64 mirror of the Lanczos quadrature (include/tsgu_hip_quadrature.h) and the test matrices of sparse_logdet, in numpy.
 
 Nothing here imports the package: the mirror is written from the header's text — the entries of T from (alpha, beta), the
 per-column length rule, `numpy.linalg.eigh` for the nodes and weights, the probe hash — so that it can disagree with the code.

@@ -1,12 +1,11 @@
 """`sparse_coloring`, the coloured `sparse_ilu0` / `sparse_ic0` and `sparse_sgs` without a GPU: the torch-op forms of `_cpu.py` against
-the plain numpy reference (tests/_coloring_ref.py), the staged header csrc/tsgu_hip_color.h against its ctypes table and the
-library, and the refusals of the public functions.
+the plain numpy reference (tests/_coloring_ref.py), the geometry query and the host refusals of include/tsgu_hip_color.h, and the
+refusals of the public functions.
 
 The error bounds are derived in `_coloring_ref`'s docstring.  `_trsm_ref.emulate` (random summation order in the value type) is held
 against the same bounds on the same inputs: they are neither vacuous nor unreachable."""
 
 import ctypes
-import os
 import warnings
 
 import numpy as np
@@ -21,8 +20,6 @@ import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, _cpu, _pattern
 from torchsparsegradutils_amd.utils import BICGSTABSettings, GMRESSettings, bicgstab, gmres, last_solve_info, linear_cg
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_color.h")
-ENTRIES = ("tsgu_color_geometry", "tsgu_csr_color_round", "tsgu_csr_color_check", "tsgu_csr_color_sweep")
 NP = {"f32": np.float32, "f64": np.float64}
 TD = {"f32": torch.float32, "f64": torch.float64}
 
@@ -68,30 +65,7 @@ def test_refusals():
         tsgu.sparse_sgs(csr(*CR.case("star300")[:2]))
 
 
-# ---- the staged header ----------------------------------------------------------------------------------------------------------------
-
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_COLOR == {"tsgu_hip_color.h": _backend.SIGNATURES_COLOR}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES)
-    assert not any(set(_backend.STAGED_COLOR) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_COLOR)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_color.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_COLOR)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_COLOR[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-
+# ---- the entries of include/tsgu_hip_color.h --------------------------------------------------------------------------------------------
 
 def test_geometry_and_host_refusals():
     widths, window, sweep_widths, tile = _backend.color_geometry()

@@ -1,5 +1,5 @@
-"""`gmres` without a GPU: the public surface, the staged header csrc/tsgu_hip_gmres.h against its ctypes table and the library, the
-host refusals of every launcher (fake pointers, device = -1: nothing is dereferenced), and the torch-op path on CPU tensors in
+"""`gmres` without a GPU: the public surface, the geometry query and the host refusals of every launcher of include/tsgu_hip_gmres.h
+(fake pointers, device = -1: nothing is dereferenced), and the torch-op path on CPU tensors in
 fp64 against the mirror (tests/_gmres_ref.py) and numpy.linalg.solve.
 
 The solution bound is derived: a column returns only with a true residual of at most threshold_c = max(abstol, reltol |r0|) (or at
@@ -8,7 +8,6 @@ Iteration counts are compared with the mirror's at tolerances where every decisi
 """
 
 import ctypes
-import os
 import sys
 
 import numpy as np
@@ -20,9 +19,7 @@ import _gmres_ref as GR
 from torchsparsegradutils_amd import _backend, utils
 from torchsparsegradutils_amd.utils import GMRESSettings, gmres, gmres_t, last_solve_info
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_gmres.h")
-ENTRIES = ("tsgu_gmres_geometry", "tsgu_gmres_project", "tsgu_gmres_subtract", "tsgu_gmres_scale", "tsgu_gmres_scalar",
-           "tsgu_gmres_update")
+HEADER = "tsgu_hip_gmres.h"
 U = 2.0 ** -53
 
 
@@ -47,30 +44,7 @@ def test_surface():
     assert last_solve_info("gmres")["fused"] is False
 
 
-# ---- the staged header --------------------------------------------------------------------------------------------------------------
-
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_GMRES == {"tsgu_hip_gmres.h": _backend.SIGNATURES_GMRES}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG)
-    assert not any(set(_backend.STAGED_GMRES) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_GMRES)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_gmres.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_GMRES)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_GMRES[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-
+# ---- the entries of include/tsgu_hip_gmres.h ----------------------------------------------------------------------------------------
 
 def test_geometry():
     for td, wide in ((torch.float32, 4), (torch.float64, 2)):
@@ -116,7 +90,7 @@ def _call(name, **changes):
 
 @pytest.mark.parametrize("name", list(BASE))
 def test_host_refusals(name):
-    params = dict(A.prototypes(STAGED_HEADER))[name]
+    params = dict(A.prototypes(HEADER))[name]
     assert [q[0] for q in params[:-2]] == list(BASE[name]), "the base call names the header's parameters"
     cap = _backend.gmres_geometry(torch.float32, 8, 4)[0]
     assert _call(name) == A.BAD_ARG, "device = -1 is refused (and nothing before it)"

@@ -3,7 +3,7 @@ restatement in tests/_expm_ref.py.
 
 The bound is a count of roundings, not a measurement.  With eps the machine epsilon of the value type, every output element is
 within R·eps·M of the float64 result on the same (rounded) inputs, M the sum of the absolute values of the terms the element is
-computed from, and R read off the expressions of csrc/tsgu_hip_expm.h:
+computed from, and R read off the expressions of include/tsgu_hip_expm.h:
 
   step      t0 = gamma·prev (1), t1 = fma(beta, x, −t0) (1), t2 = fma(alpha, prod, t1) (1 when prod is given), new = t2 + src (1 when
             src is given): R = 2 + [prod] + [src].  alpha, beta and gamma are cast to the value type once; the test passes values
@@ -213,7 +213,7 @@ def test_a_unit_coefficient_returns_the_bits():
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------
 
 def test_refusals_launch_nothing():
-    """Each refusal csrc/tsgu_hip_expm.h names returns its code; the buffers of a refused launch keep their bits."""
+    """Each refusal include/tsgu_hip_expm.h names returns its code; the buffers of a refused launch keep their bits."""
     lib = _backend.load_library()
     tcap, ccap = _caps()
     n, p, m, T = 37, 8, 3, 2

@@ -5,8 +5,6 @@ results must be EQUAL to the restatement's (a bfloat16 result is the exact value
 counted-roundings bound of tests/test_gpu_sparse_bsr_mm.py (`_bound`, restated here): the terms really added are k / 2 for the
 forward, m for Aᵀ·G and p for the SDDMM; stored zeros add no error."""
 
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -20,7 +18,7 @@ from torchsparsegradutils_amd import sparse_semi_structured as mod
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
-HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_semi.h")
+HEADER = "tsgu_hip_semi.h"
 F64 = torch.float64
 BF16 = torch.bfloat16
 EPS = {torch.float32: 2.0 ** -24, torch.float64: 2.0 ** -53}

@@ -1,11 +1,10 @@
-"""sparse_amg without a GPU: the exports, every refusal, the staged C-ABI header against `_backend.SIGNATURES_AMG` and the library,
-the host-side refusals of the three launchers and the geometry query, and the CPU path (the same Python code over the torch-op
+"""sparse_amg without a GPU: the exports, every refusal, the host-side refusals of the three launchers and the geometry query of
+include/tsgu_hip_amg.h, and the CPU path (the same Python code over the torch-op
 primitives of `_cpu.py`) against the numpy oracle `_amg_ref.py`: aggregates exactly, prolongators, operators and the cycle within
 1e-12, the retry rule, symmetry, `refresh`, a matrix that does not coarsen, and the iteration count of a preconditioned CG."""
 
 import ctypes
 import functools
-import os
 import warnings
 
 import numpy as np
@@ -16,9 +15,6 @@ import _abi_cases as A
 import _amg_ref as ar
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import SparseAMG, _backend, sparse_amg
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGED_HEADER = os.path.join(ROOT, "torchsparsegradutils_amd", "csrc", "tsgu_hip_amg.h")
 
 # name -> (lattice, weights, theta, coarse_size)
 CASES = {
@@ -142,32 +138,7 @@ def test_object_protocol():
         assert agg.shape == (lv["n"],) and not agg.dtype.is_floating_point and int(agg.max()) == lv["aggregates"] - 1
 
 
-# ---- the staged header ----------------------------------------------------------------------------------------------------------------
-
-ENTRIES = ("tsgu_amg_geometry", "tsgu_csr_amg_hop", "tsgu_amg_mis2_update", "tsgu_csr_affine_spmm")
-
-
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_AMG == {"tsgu_hip_amg.h": _backend.SIGNATURES_AMG}
-    assert not set(_backend.STAGED_AMG) & (set(_backend.ABI) | set(_backend.STAGED))
-    names = set(_backend.SIGNATURES_AMG)
-    assert not any(names & set(table) for table in (*_backend.ABI.values(), *_backend.STAGED.values()))
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_amg.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_AMG)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_AMG[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-
+# ---- the entries of include/tsgu_hip_amg.h ----------------------------------------------------------------------------------------------
 
 def test_geometry():
     widths, tile = _backend.amg_geometry()

@@ -1,37 +1,21 @@
 """sparse_banded_triangular_solve without a GPU: the validation of sparse_triangular_solve, CPU operands, the widths band_plan reports
-and the staged header against its ctypes table and the library."""
-
-import ctypes
-import os
+and the geometry queries of include/tsgu_hip_band.h."""
 
 import numpy as np
 import pytest
 import torch
 
-import _abi_cases as A
 import _trsm_ref as R
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, _pattern
-
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_band.h")
-ENTRIES = ("tsgu_csr_band_geometry", "tsgu_csr_band_sptrsm_work_bytes", "tsgu_csr_band_sptrsm")
-
 
 def csr(ptr, idx, val):
     n = len(ptr) - 1
     return torch.sparse_csr_tensor(torch.from_numpy(ptr), torch.from_numpy(idx), torch.from_numpy(val), (n, n))
 
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_BAND == {"tsgu_hip_band.h": _backend.SIGNATURES_BAND}
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_BAND)
-    raw, lib = ctypes.CDLL(_backend.LIB_PATH), _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_BAND[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
+def test_geometry():
+    lib = _backend.load_library()
     assert _backend.band_geometry(torch.float32, 1 << 20, 8, 3) == (64, 32, 256)
     assert lib.tsgu_csr_band_sptrsm_work_bytes(_backend.TSGU_F32, 1 << 20, 8, 9, 0, 0) == 0          # wider than the cap
 

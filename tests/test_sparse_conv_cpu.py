@@ -1,9 +1,5 @@
 """neighbor_mm / voxel_neighbors / kernel_offsets without a GPU: the torch-op path of _cpu.py against the float64 reference
-(tests/_conv_ref.py), the tables against a dictionary lookup, the refusals, and the staged header csrc/tsgu_hip_conv.h against its
-ctypes table and the library."""
-
-import ctypes
-import os
+(tests/_conv_ref.py), the tables against a dictionary lookup, the refusals, and the geometry query of include/tsgu_hip_conv.h."""
 
 import pytest
 import torch
@@ -12,10 +8,6 @@ import _abi_cases as A
 import _conv_ref as cr
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend
-
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_conv.h")
-ENTRIES = ("tsgu_neighbor_mm_geometry", "tsgu_neighbor_mm", "tsgu_neighbor_mm_grad_w")
-
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("n_in,n_out,K,d1,d2", [(200, 257, 5, 20, 17), (200, 127, 27, 4, 6), (40, 40, 1, 1, 1), (0, 9, 3, 4, 5)])
@@ -84,28 +76,8 @@ def test_refusals():
         tsgu.voxel_neighbors(torch.zeros(3, 5, dtype=torch.int64), torch.zeros(2, 5, dtype=torch.int64))
 
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_CONV == {"tsgu_hip_conv.h": _backend.SIGNATURES_CONV}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE,
-              _backend.STAGED_CIQ, _backend.STAGED_EXPM, _backend.STAGED_TOPK, _backend.STAGED_SEMI, _backend.STAGED_SINKHORN,
-              _backend.STAGED_SEMIRING, _backend.STAGED_GAT)
-    assert not any(set(_backend.STAGED_CONV) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_CONV)
-    assert not any(names & set(table) for reg in others for table in reg.values()), "no shared names"
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_conv.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_CONV)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
+def test_geometry():
     lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_CONV[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-        if name != "tsgu_neighbor_mm_geometry":
-            assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
     # the geometry the GPU tests take their summation lengths from: 256-row chunks until the launch has 2048 workgroups
     assert _backend.neighbor_mm_geometry(torch.float32, 700, 27, 70, 45) == (128, 256, 3, 3 * 27 * 70 * 45 * 4)
     assert _backend.neighbor_mm_geometry(torch.float64, 256, 9, 130, 33) == (128, 256, 1, 16)

@@ -1,6 +1,6 @@
 """`sparse_expm_mm` without a GPU: the coefficient rule against the exponential it expands, the torch-op path on CPU tensors in fp64
-against `torch.linalg.matrix_exp` and `torch.autograd.gradcheck`, layouts, index types, every refusal, the staged header
-csrc/tsgu_hip_expm.h against its ctypes table and the library, and the host refusals of the launchers (fake pointers, device = -1:
+against `torch.linalg.matrix_exp` and `torch.autograd.gradcheck`, layouts, index types, every refusal, and the geometry
+query and the host refusals of the launchers of include/tsgu_hip_expm.h (fake pointers, device = -1:
 nothing is dereferenced).
 
 Bounds.  The coefficient test holds Σ_k c_k T_k(x) against exp(t(ρx + mid)) on 2001 points of [−1, 1] within the method's own
@@ -26,8 +26,7 @@ import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_expm_mm
 from torchsparsegradutils_amd.sparse_expm import SparseExpmMM, _coefficients, _ive
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_expm.h")
-ENTRIES = ("tsgu_expm_geometry", "tsgu_cheb_step", "tsgu_cheb_combine")
+HEADER = "tsgu_hip_expm.h"
 F64 = torch.float64
 EPS = float(np.finfo(np.float64).eps)
 TOL = 1e-13
@@ -379,35 +378,11 @@ def test_double_backward_raises():
         g.sum().backward()
 
 
-# ---- the staged header --------------------------------------------------------------------------------------------------------------
+# ---- the entries of include/tsgu_hip_expm.h -----------------------------------------------------------------------------------------
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_EXPM == {"tsgu_hip_expm.h": _backend.SIGNATURES_EXPM}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE,
-              _backend.STAGED_CIQ)
-    assert len(others) + 1 == 8, "the eight registries"
-    assert not any(set(_backend.STAGED_EXPM) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_EXPM)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    every = [name for reg in others for table in reg.values() for name in table]
-    assert len(every) == len(set(every)), "the eight registries are disjoint"
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_expm.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_EXPM)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_EXPM[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    src = os.path.join(os.path.dirname(STAGED_HEADER), "expm.hip")
-    assert os.path.exists(src) and '#include "tsgu_hip_expm.h"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+def test_the_translation_unit_includes_the_header():
+    src = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "expm.hip")
+    assert os.path.exists(src) and f'#include "../../include/{HEADER}"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
 
 
 def test_geometry():
@@ -447,7 +422,7 @@ def _call(name, **changes):
 
 @pytest.mark.parametrize("name", list(BASE))
 def test_host_refusals(name):
-    params = dict(A.prototypes(STAGED_HEADER))[name]
+    params = dict(A.prototypes(HEADER))[name]
     assert [q[0] for q in params[:-2]] == list(BASE[name]), "the base call names the header's parameters"
     tcap, ccap = _backend.expm_geometry(torch.float32, 100, 16)[:2]
     assert _call(name) == A.BAD_ARG, "device = -1 is refused (and nothing before it)"

@@ -1,11 +1,8 @@
 """sparse_gat_attention / sparse_gatv2_attention without a GPU: the torch-op path of _cpu.py against the dense float64 oracle
-(tests/_gat_ref.py), the refusals, and the staged header csrc/tsgu_hip_gat.h against its ctypes table and the library.
+(tests/_gat_ref.py), the refusals, and the geometry query of include/tsgu_hip_gat.h.
 
 float64 comparisons at rtol 1e-12: both sides sum at most 19 terms of magnitude O(10) on a grid of 1/32.
 """
-
-import ctypes
-import os
 
 import pytest
 import torch
@@ -14,8 +11,6 @@ import _abi_cases as A
 import _gat_ref as gr
 from torchsparsegradutils_amd import _backend, sparse_gat_attention, sparse_gatv2_attention
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_gat.h")
-ENTRIES = ("tsgu_gat_geometry", "tsgu_csr_gat_forward", "tsgu_csr_gat_backward_rows", "tsgu_csr_gat_backward_cols", "tsgu_gat_fold")
 N, M = 23, 19
 FN = {"gat": sparse_gat_attention, "gatv2": sparse_gatv2_attention}
 
@@ -112,28 +107,8 @@ def test_refusals():
     assert not _backend.gat_supported(torch.float16, 1, 8)
 
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_GAT == {"tsgu_hip_gat.h": _backend.SIGNATURES_GAT}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE,
-              _backend.STAGED_CIQ, _backend.STAGED_EXPM, _backend.STAGED_TOPK, _backend.STAGED_SEMI, _backend.STAGED_SINKHORN,
-              _backend.STAGED_SEMIRING)
-    assert not any(set(_backend.STAGED_GAT) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_GAT)
-    assert not any(names & set(table) for reg in others for table in reg.values()), "no shared names"
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_gat.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_GAT)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
+def test_geometry():
     lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_GAT[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-        if name != "tsgu_gat_geometry":
-            assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
     # the geometry the GPU tests size their cases from: the stage shrinks with the heads of a tile, to 128 (fp64: 128) at H = 128
     assert _backend.gat_geometry(torch.float32, "gat", 1, 64) == (4, 1024, 64)
     assert _backend.gat_geometry(torch.float32, "gat", 128, 8) == (4, 128, 256)

@@ -1,10 +1,9 @@
 """sparse_lobpcg without a GPU: the numpy restatement on every case, the public API on CPU operands against the float64 spectrum
-(eigenvalues, orthonormality, gradient, gradcheck), the restart path, every refusal, the staged C-ABI header against
-`_backend.SIGNATURES_LOBPCG`, and the host-side refusals of the three launchers."""
+(eigenvalues, orthonormality, gradient, gradcheck), the restart path, every refusal, and the geometry query and host-side refusals
+of the three launchers of include/tsgu_hip_lobpcg.h."""
 
 import ctypes
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -15,8 +14,6 @@ import _lobpcg_ref as lr
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_lobpcg, utils
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGED_HEADER = os.path.join(ROOT, "torchsparsegradutils_amd", "csrc", "tsgu_hip_lobpcg.h")
 DTYPES = {"float32": (torch.float32, np.float32), "float64": (torch.float64, np.float64)}
 OPERANDS = [("coo", torch.int64), ("csr", torch.int32), ("csr", torch.int64)]
 
@@ -268,29 +265,7 @@ def test_refusals():
         sparse_lobpcg(Asp, 3, X=X, preconditioner="jacobi")
 
 
-# ---- the staged header ------------------------------------------------------------------------------------------------------------
-
-ENTRIES = ("tsgu_tall_geometry", "tsgu_tall_gram", "tsgu_tall_combine", "tsgu_lobpcg_residual")
-
-
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED == {"tsgu_hip_lobpcg.h": _backend.SIGNATURES_LOBPCG}
-    assert not set(_backend.STAGED) & set(_backend.ABI) and not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_lobpcg.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_LOBPCG)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_LOBPCG[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7
-
+# ---- the entries of include/tsgu_hip_lobpcg.h -------------------------------------------------------------------------------------
 
 def test_geometry():
     kmax, wmax, rows, nbytes = _backend.tall_geometry(torch.float32, 10 * 2048 + 1, 96, 96)

@@ -1,5 +1,5 @@
-"""`sparse_logdet` / `sparse_inv_quad_logdet` without a GPU: the public surface and every refusal, the staged header
-csrc/tsgu_hip_quadrature.h against its ctypes table and the library, the host refusals of both launchers (fake pointers,
+"""`sparse_logdet` / `sparse_inv_quad_logdet` without a GPU: the public surface and every refusal, the geometry
+query and the host refusals of both launchers of include/tsgu_hip_quadrature.h (fake pointers,
 device = -1: nothing is dereferenced), the probe function against its mirror, and the torch-op path on CPU tensors in fp64 against
 `slogdet`, `inv` and `torch.autograd.gradcheck`.
 
@@ -11,7 +11,6 @@ tolerance: |estimate - exact| <= 4 stderr fails for a correct estimator with pro
 """
 
 import ctypes
-import os
 import warnings
 
 import numpy as np
@@ -24,8 +23,7 @@ import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, _cpu, sparse_inv_quad_logdet, sparse_logdet
 from torchsparsegradutils_amd.utils._operator import LAST_SOLVE
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_quadrature.h")
-ENTRIES = ("tsgu_quadrature_geometry", "tsgu_tridiag_quadrature", "tsgu_rademacher_fill")
+HEADER = "tsgu_hip_quadrature.h"
 F64 = torch.float64
 
 
@@ -113,30 +111,7 @@ def test_double_backward_raises():
         g.coalesce().values().sum().backward()
 
 
-# ---- the staged header --------------------------------------------------------------------------------------------------------------
-
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_QUADRATURE == {"tsgu_hip_quadrature.h": _backend.SIGNATURES_QUADRATURE}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR)
-    assert not any(set(_backend.STAGED_QUADRATURE) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_QUADRATURE)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_quadrature.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_QUADRATURE)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_QUADRATURE[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-
+# ---- the entries of include/tsgu_hip_quadrature.h -----------------------------------------------------------------------------------
 
 def test_geometry():
     cap, work = _backend.quadrature_geometry()
@@ -166,7 +141,7 @@ def _call(name, **changes):
 
 @pytest.mark.parametrize("name", list(BASE))
 def test_host_refusals(name):
-    params = dict(A.prototypes(STAGED_HEADER))[name]
+    params = dict(A.prototypes(HEADER))[name]
     assert [q[0] for q in params[:-2]] == list(BASE[name]), "the base call names the header's parameters"
     cap = _backend.quadrature_geometry()[0]
     assert _call(name) == A.BAD_ARG, "device = -1 is refused (and nothing before it)"

@@ -1,19 +1,13 @@
 """sparse_selected_inverse / cholesky_pattern / marginal_variance without a GPU: _cpu.selected_inverse against the dense float64
-inverse (tests/_selinv_ref.py), the error behaviour, the refusals, and the staged header against its ctypes table and the library."""
-
-import ctypes
-import os
+inverse (tests/_selinv_ref.py), the error behaviour and the refusals."""
 
 import pytest
 import torch
 
-import _abi_cases as A
 import _selinv_ref as R
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_selinv.h")
-ENTRIES = ("tsgu_csc_selinv_work_bytes", "tsgu_csc_selinv_geometry", "tsgu_csc_selinv")
 CPU = torch.device("cpu")
 
 
@@ -71,16 +65,3 @@ def test_refusals_and_the_grad_guard():
 @pytest.mark.parametrize("layout", [torch.sparse_coo, torch.sparse_csr])
 def test_marginal_variance(layout, ldlt):
     R.check_marginal_variance(layout, ldlt, CPU)
-
-
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_SELINV == {"tsgu_hip_selinv.h": _backend.SIGNATURES_SELINV}
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_SELINV)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_SELINV[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name

@@ -1,6 +1,6 @@
 """The 2:4 semi-structured operand without a GPU: prune, indices and to_dense of the torch-op path against the numpy restatement
-(tests/_semi_ref.py), the gradients against `torch.autograd.gradcheck`, every refusal, the staged header csrc/tsgu_hip_semi.h against
-its ctypes table and the library, and the host refusals of the launchers (fake pointers, device = -1: nothing is dereferenced)."""
+(tests/_semi_ref.py), the gradients against `torch.autograd.gradcheck`, every refusal, the flag values of include/tsgu_hip_semi.h, its
+geometry query and the host refusals of its launchers (fake pointers, device = -1: nothing is dereferenced)."""
 
 import ctypes
 import os
@@ -15,8 +15,7 @@ import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import (SemiStructured, _backend, sparse_semi_structured_linear, sparse_semi_structured_mm,
                                       sparse_semi_structured_prune)
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_semi.h")
-ENTRIES = ("tsgu_semi_geometry", "tsgu_semi_prune", "tsgu_semi_expand", "tsgu_semi_mm", "tsgu_semi_mm_t", "tsgu_semi_sddmm")
+HEADER = "tsgu_hip_semi.h"
 DTYPES = [torch.float32, torch.float64, torch.bfloat16]
 IDS = ["f32", "f64", "bf16"]
 F64 = torch.float64
@@ -222,35 +221,12 @@ def test_gpu_kernels_refuse_cpu_tensors():
         _backend.semi_mm(S.values, S.meta, 8, torch.randn(8, 2), None, False, True)
 
 
-# ---- the staged header ----------------------------------------------------------------------------------------------------------------
+# ---- the entries of include/tsgu_hip_semi.h -------------------------------------------------------------------------------------------
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_SEMI == {"tsgu_hip_semi.h": _backend.SIGNATURES_SEMI}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE,
-              _backend.STAGED_CIQ, _backend.STAGED_EXPM, _backend.STAGED_TOPK)
-    assert len(others) + 1 == 10, "the ten registries"
-    assert not any(set(_backend.STAGED_SEMI) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_SEMI)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    every = [name for reg in others for table in reg.values() for name in table]
-    assert len(every) == len(set(every)), "the registries are disjoint"
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_semi.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_SEMI)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_SEMI[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for _, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")]
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    src = os.path.join(os.path.dirname(STAGED_HEADER), "semi.hip")
-    assert os.path.exists(src) and '#include "tsgu_hip_semi.h"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+def test_the_header_flags_and_the_translation_unit():
+    src = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "semi.hip")
+    assert os.path.exists(src) and f'#include "../../include/{HEADER}"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+    text = open(os.path.join(A.INCLUDE, HEADER)).read()
     assert (_backend.SEMI_DENSE_T, _backend.SEMI_OUT_T) == (1, 2)
     assert "#define TSGU_SEMI_DENSE_T 1" in text and "#define TSGU_SEMI_OUT_T 2" in text
 
@@ -294,7 +270,7 @@ def _call(name, **changes):
 
 @pytest.mark.parametrize("name", list(BASES))
 def test_host_refusals(name):
-    params = dict(A.prototypes(STAGED_HEADER))[name]
+    params = dict(A.prototypes(HEADER))[name]
     base = BASES[name]
     assert [q[0] for q in params[:-2]] == list(base), "the base call names the header's parameters"
     assert _call(name) == A.BAD_ARG, "device = -1 is refused (and nothing before it)"

@@ -1,6 +1,6 @@
 """sparse_sinkhorn without a GPU: the torch-op path against the dense float64 restatement (tests/_sinkhorn_ref.py) in values,
 potentials and all three gradients, the entry-wise restatement against the dense one, the result's index tensors, the refusals,
-and the staged header csrc/tsgu_hip_sinkhorn.h against its ctypes table and the library.
+and the host refusals of the entries of include/tsgu_hip_sinkhorn.h.
 
 Tolerance of the float64 comparisons.  Both sides compute the same T iterations in float64; the half-step maps are non-expansive
 in the sup norm, so the roundings of the 2T half steps add: at most 2T·c·ε·M with ε = 2⁻⁵³, c ≤ 53 + 10 roundings on an entry's
@@ -21,8 +21,6 @@ import _sinkhorn_ref as ref
 import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_sinkhorn
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_sinkhorn.h")
-ENTRIES = ("tsgu_sinkhorn_workspace", "tsgu_sinkhorn_half", "tsgu_sinkhorn_plan", "tsgu_sinkhorn_half_backward", "tsgu_segment_sum")
 F64 = torch.float64
 N, M = 37, 53
 POT_TOL, GRAD_TOL = 1e-11, 1e-9
@@ -348,33 +346,11 @@ def test_refusals():
         sparse_sinkhorn(batched, la, None)
 
 
-# ---- the staged header ----------------------------------------------------------------------------------------------------------------
+# ---- the entries of include/tsgu_hip_sinkhorn.h ---------------------------------------------------------------------------------------
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_SINKHORN == {"tsgu_hip_sinkhorn.h": _backend.SIGNATURES_SINKHORN}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE,
-              _backend.STAGED_CIQ, _backend.STAGED_EXPM, _backend.STAGED_TOPK, _backend.STAGED_SEMI)
-    assert len(others) + 1 == 11, "the eleven registries"
-    assert not any(set(_backend.STAGED_SINKHORN) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_SINKHORN)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_sinkhorn.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_SINKHORN)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_SINKHORN[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-        if name != "tsgu_sinkhorn_workspace":
-            assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    src = os.path.join(os.path.dirname(STAGED_HEADER), "sinkhorn.hip")
-    assert os.path.exists(src) and '#include "tsgu_hip_sinkhorn.h"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+def test_the_translation_unit_includes_the_header():
+    src = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "sinkhorn.hip")
+    assert os.path.exists(src) and '#include "../../include/tsgu_hip_sinkhorn.h"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
 
 
 def test_host_refusals_of_the_entries():

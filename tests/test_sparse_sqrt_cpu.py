@@ -1,6 +1,6 @@
 """`sparse_inv_sqrt_mm` / `sparse_sqrt_mm` without a GPU: the quadrature rule against scipy and against its own scalar error, the
-torch-op path on CPU tensors in fp64 against dense `eigh` and `torch.autograd.gradcheck`, the bounds estimate, every refusal, the
-staged header csrc/tsgu_hip_ciq.h against its ctypes table and the library, and the host refusals of the launchers (fake pointers,
+torch-op path on CPU tensors in fp64 against dense `eigh` and `torch.autograd.gradcheck`, the bounds estimate, every refusal, and
+the geometry query and the host refusals of the launchers of include/tsgu_hip_ciq.h (fake pointers,
 device = -1: nothing is dereferenced).
 
 Bounds.  The rule's nodes and weights match scipy's elliptic functions to 1e-12 relative (both evaluate (u | m') for the same rounded
@@ -24,8 +24,7 @@ import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_inv_sqrt_mm, sparse_sqrt_mm
 from torchsparsegradutils_amd.sparse_sqrt import SparseInvSqrtMM, _ciq_rule
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_ciq.h")
-ENTRIES = ("tsgu_ciq_geometry", "tsgu_ciq_update", "tsgu_ciq_stop")
+HEADER = "tsgu_hip_ciq.h"
 F64 = torch.float64
 SEEDS = tuple(range(8))
 
@@ -289,31 +288,11 @@ def test_double_backward_raises():
         g.sum().backward()
 
 
-# ---- the staged header --------------------------------------------------------------------------------------------------------------
+# ---- the entries of include/tsgu_hip_ciq.h ------------------------------------------------------------------------------------------
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_CIQ == {"tsgu_hip_ciq.h": _backend.SIGNATURES_CIQ}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE)
-    assert not any(set(_backend.STAGED_CIQ) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_CIQ)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_ciq.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_CIQ)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_CIQ[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    for name, params in protos[1:]:
-        assert params[-2:] == [("device", "int"), ("stream", "void*")], name
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    src = os.path.join(os.path.dirname(STAGED_HEADER), "ciq.hip")
-    assert os.path.exists(src) and '#include "tsgu_hip_ciq.h"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+def test_the_translation_unit_includes_the_header():
+    src = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "ciq.hip")
+    assert os.path.exists(src) and f'#include "../../include/{HEADER}"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
 
 
 def test_geometry():
@@ -352,7 +331,7 @@ def _call(name, **changes):
 
 @pytest.mark.parametrize("name", list(BASE))
 def test_host_refusals(name):
-    params = dict(A.prototypes(STAGED_HEADER))[name]
+    params = dict(A.prototypes(HEADER))[name]
     assert [q[0] for q in params[:-2]] == list(BASE[name]), "the base call names the header's parameters"
     cap = _backend.ciq_geometry(torch.float32, 100, 16)[0]
     assert _call(name) == A.BAD_ARG, "device = -1 is refused (and nothing before it)"

@@ -1,6 +1,6 @@
 """sparse_topk_mm without a GPU: the torch-op path against the numpy restatement (tests/_topk_ref.py), the gradients against
-`torch.autograd.gradcheck` and the dense `topk` composition, every refusal, the staged header csrc/tsgu_hip_topk.h against its ctypes
-table and the library, and the host refusals of the launcher (fake pointers, device = -1: nothing is dereferenced).
+`torch.autograd.gradcheck` and the dense `topk` composition, every refusal, the flag values of include/tsgu_hip_topk.h, its geometry
+query and the host refusals of its launcher (fake pointers, device = -1: nothing is dereferenced).
 
 The exact cases hold integers in [−3, 3] (every product and sum is exact in float32, float64 and bfloat16's float32 accumulator), so
 crow, col and the values must be EQUAL to the restatement's; a bfloat16 value is the exact score rounded once."""
@@ -18,8 +18,7 @@ import torchsparsegradutils_amd as tsgu
 from torchsparsegradutils_amd import _backend, sparse_topk_mm
 from torchsparsegradutils_amd.sparse_topk import nnz_of, row_counts
 
-STAGED_HEADER = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "tsgu_hip_topk.h")
-ENTRIES = ("tsgu_topk_geometry", "tsgu_topk_mm")
+HEADER = "tsgu_hip_topk.h"
 DTYPES = [torch.float32, torch.float64, torch.bfloat16]
 IDS = ["f32", "f64", "bf16"]
 F64 = torch.float64
@@ -251,34 +250,12 @@ def test_the_cap_on_k_is_named_for_gpu_operands(monkeypatch):
         sparse_topk_mm(Q, K, cap + 1)
 
 
-# ---- the staged header ----------------------------------------------------------------------------------------------------------------
+# ---- the entries of include/tsgu_hip_topk.h -------------------------------------------------------------------------------------------
 
-def test_the_staged_header_is_bound():
-    assert _backend.STAGED_TOPK == {"tsgu_hip_topk.h": _backend.SIGNATURES_TOPK}
-    others = (_backend.ABI, _backend.STAGED, _backend.STAGED_AMG, _backend.STAGED_GMRES, _backend.STAGED_COLOR, _backend.STAGED_QUADRATURE,
-              _backend.STAGED_CIQ, _backend.STAGED_EXPM)
-    assert len(others) + 1 == 9, "the nine registries"
-    assert not any(set(_backend.STAGED_TOPK) & set(reg) for reg in others)
-    names = set(_backend.SIGNATURES_TOPK)
-    assert not any(names & set(table) for reg in others for table in reg.values())
-    every = [name for reg in others for table in reg.values() for name in table]
-    assert len(every) == len(set(every)), "the registries are disjoint"
-    assert not os.path.exists(os.path.join(A.INCLUDE, "tsgu_hip_topk.h"))
-    protos = A.prototypes(STAGED_HEADER)
-    assert tuple(n for n, _ in protos) == ENTRIES == tuple(_backend.SIGNATURES_TOPK)
-    raw = ctypes.CDLL(_backend.LIB_PATH)
-    lib = _backend.load_library()
-    for name, params in protos:
-        assert hasattr(raw, name), f"{name} is declared in the staged header but not exported by libtsgu_hip.so"
-        restype, argtypes = _backend.SIGNATURES_TOPK[name]
-        assert [A.klass_of_ctype(t) for t in argtypes] == [A.klass_of_decl(t) for _, t in params], name
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype == restype, name
-    assert protos[1][1][-2:] == [("device", "int"), ("stream", "void*")]
-    text = open(STAGED_HEADER).read()
-    assert '#include "../../include/tsgu_hip.h"' in text and "TSGU_ABI_VERSION" in text
-    assert lib.tsgu_abi_version() == 7 == _backend.ABI_VERSION
-    src = os.path.join(os.path.dirname(STAGED_HEADER), "topk.hip")
-    assert os.path.exists(src) and '#include "tsgu_hip_topk.h"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+def test_the_header_flags_and_the_translation_unit():
+    src = os.path.join(os.path.dirname(os.path.abspath(_backend.__file__)), "csrc", "topk.hip")
+    assert os.path.exists(src) and f'#include "../../include/{HEADER}"' in open(src).read(), "the translation unit the Makefile's wildcard picks up"
+    text = open(os.path.join(A.INCLUDE, HEADER)).read()
     assert (_backend.TOPK_CAUSAL, _backend.TOPK_EXCLUDE_SELF) == (1, 2)
     assert "#define TSGU_TOPK_CAUSAL 1" in text and "#define TSGU_TOPK_EXCLUDE_SELF 2" in text
 
@@ -315,7 +292,7 @@ def _call(**changes):
 
 
 def test_host_refusals():
-    params = dict(A.prototypes(STAGED_HEADER))["tsgu_topk_mm"]
+    params = dict(A.prototypes(HEADER))["tsgu_topk_mm"]
     assert [q[0] for q in params[:-2]] == list(BASE), "the base call names the header's parameters"
     cap = _backend.topk_geometry(torch.float32)[0]
     assert _call() == A.BAD_ARG, "device = -1 is refused (and nothing before it)"

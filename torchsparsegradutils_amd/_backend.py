@@ -244,6 +244,151 @@ SIGNATURES_FSAI = {
     "tsgu_csr_fsai": (_int, [_int, _int, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _int, _int, _ptr]),
 }
 
+# the additive entries of include/tsgu_hip_lobpcg.h (same library, same ABI version)
+SIGNATURES_LOBPCG = {
+    "tsgu_tall_geometry": (_int, [_int, _i64, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_i64)]),
+    "tsgu_tall_gram": (_int, [_int, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _int, _int, _ptr]),
+    "tsgu_tall_combine": (_int, [_int, _i64, _int, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_lobpcg_residual": (_int, [_int, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _int, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_amg.h (same library, same ABI version)
+SIGNATURES_AMG = {
+    "tsgu_amg_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_amg_hop": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_amg_mis2_update": (_int, [_int, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_csr_affine_spmm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _dbl,
+                                    _ptr, _i64, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_gmres.h (same library, same ABI version)
+SIGNATURES_GMRES = {
+    "tsgu_gmres_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                   ctypes.POINTER(_i64)]),
+    "tsgu_gmres_project": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_gmres_subtract": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_gmres_scale": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_gmres_scalar": (_int, [_int, _int, _int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _int, _i64, _int, _ptr]),
+    "tsgu_gmres_update": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_color.h (same library, same ABI version)
+SIGNATURES_COLOR = {
+    "tsgu_color_geometry": (_int, [ctypes.POINTER(_int)] * 6),
+    "tsgu_csr_color_round": (_int, [_int, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+    "tsgu_csr_color_check": (_int, [_int, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _int, _int, _ptr]),
+    "tsgu_csr_color_sweep": (_int, [_int, _int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
+                                    _ptr, _ptr, _i64, _ptr, _i64, _ptr, _int, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_quadrature.h (same library, same ABI version)
+SIGNATURES_QUADRATURE = {
+    "tsgu_quadrature_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_i64)]),
+    "tsgu_tridiag_quadrature": (_int, [_int, _int, _int, _int, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_rademacher_fill": (_int, [_int, _i64, _i64, _i64, _ptr, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_ciq.h (same library, same ABI version)
+SIGNATURES_CIQ = {
+    "tsgu_ciq_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                 ctypes.POINTER(_i64)]),
+    "tsgu_ciq_update": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_ciq_stop": (_int, [_int, _i64, _int, _ptr, _dbl, _ptr, _ptr, _ptr, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_expm.h (same library, same ABI version)
+SIGNATURES_EXPM = {
+    "tsgu_expm_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "tsgu_cheb_step": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _dbl, _ptr, _int, _int, _ptr, _int, _int, _ptr, _int, _ptr]),
+    "tsgu_cheb_combine": (_int, [_int, _int, _int, _i64, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _ptr, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_topk.h (same library, same ABI version)
+SIGNATURES_TOPK = {
+    "tsgu_topk_geometry": (_int, [_int, _i64, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_topk_mm": (_int, [_int, _ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _dbl, _int, _i64, _ptr, _ptr, _ptr, _int, _i64, _i64, _i64,
+                            _i64, _i64, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_semi.h (same library, same ABI version)
+SIGNATURES_SEMI = {
+    "tsgu_semi_geometry": (_int, [_int, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
+                                  ctypes.POINTER(_int)]),
+    "tsgu_semi_prune": (_int, [_int, _ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _int, _ptr]),
+    "tsgu_semi_expand": (_int, [_int, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _int, _ptr]),
+    "tsgu_semi_mm": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _ptr]),
+    "tsgu_semi_mm_t": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr]),
+    "tsgu_semi_sddmm": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_sinkhorn.h (same library, same ABI version)
+SIGNATURES_SINKHORN = {
+    "tsgu_sinkhorn_workspace": (_int, [_int, _i64, ctypes.POINTER(_i64)]),
+    "tsgu_sinkhorn_half": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_sinkhorn_plan": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+    "tsgu_sinkhorn_half_backward": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int,
+                                           _ptr, _i64, _int, _ptr]),
+    "tsgu_segment_sum": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_semiring.h (same library, same ABI version)
+SIGNATURES_SEMIRING = {
+    "tsgu_semiring_geometry": (_int, [_int, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_semiring_mm": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr,
+                                    _i64, _int, _ptr]),
+    "tsgu_csr_semiring_mm_bwd_values": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64,
+                                               _ptr, _i64, _i64, _ptr, _int, _ptr]),
+    "tsgu_csr_semiring_mm_bwd_dense": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr,
+                                              _i64, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_gat.h (same library, same ABI version)
+SIGNATURES_GAT = {
+    "tsgu_gat_geometry": (_int, [_int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_gat_forward": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr,
+                                    _int, _int, _dbl, _ptr, _i64, _ptr, _int, _ptr]),
+    "tsgu_csr_gat_backward_rows": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
+                                          _ptr, _ptr, _i64, _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
+    "tsgu_csr_gat_backward_cols": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
+                                          _ptr, _ptr, _i64, _ptr, _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _int, _ptr]),
+    "tsgu_gat_fold": (_int, [_int, _ptr, _i64, _int, _int, _ptr, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_conv.h (same library, same ABI version)
+SIGNATURES_CONV = {
+    "tsgu_neighbor_mm_geometry": (_int, [_int, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                         ctypes.POINTER(_i64)]),
+    "tsgu_neighbor_mm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64,
+                                _int, _ptr]),
+    "tsgu_neighbor_mm_grad_w": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _int,
+                                       _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_selinv.h (same library, same ABI version)
+SIGNATURES_SELINV = {
+    "tsgu_csc_selinv_work_bytes": (_i64, [_int, _i64, _i64]),
+    "tsgu_csc_selinv_geometry": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csc_selinv": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_lsmr.h (same library, same ABI version)
+SIGNATURES_LSMR = {
+    "tsgu_lsmr_scal_rows": (_int, []),
+    "tsgu_lsmr_scalar": (_int, [_int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _int, _ptr]),
+    "tsgu_lsmr_vector": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
+}
+
+# the additive entries of include/tsgu_hip_band.h (same library, same ABI version)
+SIGNATURES_BAND = {
+    "tsgu_csr_band_geometry": (_int, [_int, _i64, _i64, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "tsgu_csr_band_sptrsm_work_bytes": (_i64, [_int, _i64, _i64, _int, _int, _int]),
+    "tsgu_csr_band_sptrsm": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr, _i64, _i64, _ptr, _int,
+                                    _int, _int, _ptr]),
+}
+
 # header of include/ -> its table: all that `load_library` binds (a header that is missing here would load with ctypes' default int
 # signatures; tests/test_abi_conformance_cpu.py holds this mapping against the directory)
 ABI = {
@@ -256,232 +401,25 @@ ABI = {
     "tsgu_hip_bsr_attention.h": SIGNATURES_BSR_ATTENTION,
     "tsgu_hip_factor.h": SIGNATURES_FACTOR,
     "tsgu_hip_fsai.h": SIGNATURES_FSAI,
+    "tsgu_hip_lobpcg.h": SIGNATURES_LOBPCG,
+    "tsgu_hip_amg.h": SIGNATURES_AMG,
+    "tsgu_hip_gmres.h": SIGNATURES_GMRES,
+    "tsgu_hip_color.h": SIGNATURES_COLOR,
+    "tsgu_hip_quadrature.h": SIGNATURES_QUADRATURE,
+    "tsgu_hip_ciq.h": SIGNATURES_CIQ,
+    "tsgu_hip_expm.h": SIGNATURES_EXPM,
+    "tsgu_hip_topk.h": SIGNATURES_TOPK,
+    "tsgu_hip_semi.h": SIGNATURES_SEMI,
+    "tsgu_hip_sinkhorn.h": SIGNATURES_SINKHORN,
+    "tsgu_hip_semiring.h": SIGNATURES_SEMIRING,
+    "tsgu_hip_gat.h": SIGNATURES_GAT,
+    "tsgu_hip_conv.h": SIGNATURES_CONV,
+    "tsgu_hip_selinv.h": SIGNATURES_SELINV,
+    "tsgu_hip_lsmr.h": SIGNATURES_LSMR,
+    "tsgu_hip_band.h": SIGNATURES_BAND,
 }
 
-# the additive entries of csrc/tsgu_hip_lobpcg.h (same library, same ABI version): a STAGED header, declared beside the sources
-# until it moves to include/ ("Adding a header")
-SIGNATURES_LOBPCG = {
-    "tsgu_tall_geometry": (_int, [_int, _i64, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
-                                  ctypes.POINTER(_i64)]),
-    "tsgu_tall_gram": (_int, [_int, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _int, _int, _ptr]),
-    "tsgu_tall_combine": (_int, [_int, _i64, _int, _ptr, _ptr, _ptr, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
-    "tsgu_lobpcg_residual": (_int, [_int, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _int, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after `ABI` (tests/test_sparse_lobpcg_cpu.py holds it against the header)
-STAGED = {"tsgu_hip_lobpcg.h": SIGNATURES_LOBPCG}
-
-# the additive entries of csrc/tsgu_hip_amg.h (same library, same ABI version): the second STAGED header.  It has a registry of its
-# own because tests pin `ABI` against include/ and `STAGED` to the LOBPCG table ("Adding a header")
-SIGNATURES_AMG = {
-    "tsgu_amg_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "tsgu_csr_amg_hop": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
-    "tsgu_amg_mis2_update": (_int, [_int, _i64, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
-    "tsgu_csr_affine_spmm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _dbl,
-                                    _ptr, _i64, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after `ABI` and `STAGED` (tests/test_sparse_amg_cpu.py holds it against the header)
-STAGED_AMG = {"tsgu_hip_amg.h": SIGNATURES_AMG}
-
-# the additive entries of csrc/tsgu_hip_gmres.h (same library, same ABI version): the third STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI`, `STAGED` and `STAGED_AMG`)
-SIGNATURES_GMRES = {
-    "tsgu_gmres_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
-                                   ctypes.POINTER(_i64)]),
-    "tsgu_gmres_project": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _int, _int, _ptr]),
-    "tsgu_gmres_subtract": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
-    "tsgu_gmres_scale": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
-    "tsgu_gmres_scalar": (_int, [_int, _int, _int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _int, _i64, _int, _ptr]),
-    "tsgu_gmres_update": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _i64, _ptr, _ptr, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after `ABI`, `STAGED` and `STAGED_AMG` (tests/test_gmres_cpu.py holds it
-# against the header)
-STAGED_GMRES = {"tsgu_hip_gmres.h": SIGNATURES_GMRES}
-
-# the additive entries of csrc/tsgu_hip_color.h (same library, same ABI version): the fourth STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI`, `STAGED`, `STAGED_AMG` and `STAGED_GMRES`)
-SIGNATURES_COLOR = {
-    "tsgu_color_geometry": (_int, [ctypes.POINTER(_int)] * 6),
-    "tsgu_csr_color_round": (_int, [_int, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
-    "tsgu_csr_color_check": (_int, [_int, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _int, _int, _ptr]),
-    "tsgu_csr_color_sweep": (_int, [_int, _int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
-                                    _ptr, _ptr, _i64, _ptr, _i64, _ptr, _int, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_coloring_cpu.py holds it against
-# the header)
-STAGED_COLOR = {"tsgu_hip_color.h": SIGNATURES_COLOR}
-
-# the additive entries of csrc/tsgu_hip_quadrature.h (same library, same ABI version): the fifth STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI` and the four registries above)
-SIGNATURES_QUADRATURE = {
-    "tsgu_quadrature_geometry": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_i64)]),
-    "tsgu_tridiag_quadrature": (_int, [_int, _int, _int, _int, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
-    "tsgu_rademacher_fill": (_int, [_int, _i64, _i64, _i64, _ptr, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_logdet_cpu.py holds it
-# against the header)
-STAGED_QUADRATURE = {"tsgu_hip_quadrature.h": SIGNATURES_QUADRATURE}
-
-# the additive entries of csrc/tsgu_hip_ciq.h (same library, same ABI version): the sixth STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI` and the five registries above)
-SIGNATURES_CIQ = {
-    "tsgu_ciq_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
-                                 ctypes.POINTER(_i64)]),
-    "tsgu_ciq_update": (_int, [_int, _i64, _i64, _int, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
-    "tsgu_ciq_stop": (_int, [_int, _i64, _int, _ptr, _dbl, _ptr, _ptr, _ptr, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_sqrt_cpu.py holds it against
-# the header)
-STAGED_CIQ = {"tsgu_hip_ciq.h": SIGNATURES_CIQ}
-
-# the additive entries of csrc/tsgu_hip_expm.h (same library, same ABI version): the seventh STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI` and the six registries above)
-SIGNATURES_EXPM = {
-    "tsgu_expm_geometry": (_int, [_int, _i64, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
-                                  ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
-    "tsgu_cheb_step": (_int, [_int, _i64, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _dbl, _ptr, _int, _int, _ptr, _int, _int, _ptr, _int, _ptr]),
-    "tsgu_cheb_combine": (_int, [_int, _int, _int, _i64, _i64, _int, _int, _ptr, _ptr, _ptr, _i64, _ptr, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_expm_cpu.py holds it against
-# the header)
-STAGED_EXPM = {"tsgu_hip_expm.h": SIGNATURES_EXPM}
-
-# the additive entries of csrc/tsgu_hip_topk.h (same library, same ABI version): the eighth STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI` and the seven registries above)
-SIGNATURES_TOPK = {
-    "tsgu_topk_geometry": (_int, [_int, _i64, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
-                                  ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "tsgu_topk_mm": (_int, [_int, _ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _dbl, _int, _i64, _ptr, _ptr, _ptr, _int, _i64, _i64, _i64,
-                            _i64, _i64, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_topk_cpu.py holds it against
-# the header)
-STAGED_TOPK = {"tsgu_hip_topk.h": SIGNATURES_TOPK}
-
-# the additive entries of csrc/tsgu_hip_semi.h (same library, same ABI version): the ninth STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI` and the eight registries above)
-SIGNATURES_SEMI = {
-    "tsgu_semi_geometry": (_int, [_int, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int),
-                                  ctypes.POINTER(_int)]),
-    "tsgu_semi_prune": (_int, [_int, _ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _i64, _int, _ptr]),
-    "tsgu_semi_expand": (_int, [_int, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _i64, _int, _ptr]),
-    "tsgu_semi_mm": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _ptr]),
-    "tsgu_semi_mm_t": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr]),
-    "tsgu_semi_sddmm": (_int, [_int, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_semi_structured_cpu.py holds
-# it against the header)
-STAGED_SEMI = {"tsgu_hip_semi.h": SIGNATURES_SEMI}
-
-# the additive entries of csrc/tsgu_hip_sinkhorn.h (same library, same ABI version): the tenth STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI` and the nine registries above)
-SIGNATURES_SINKHORN = {
-    "tsgu_sinkhorn_workspace": (_int, [_int, _i64, ctypes.POINTER(_i64)]),
-    "tsgu_sinkhorn_half": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
-    "tsgu_sinkhorn_plan": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
-    "tsgu_sinkhorn_half_backward": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int,
-                                           _ptr, _i64, _int, _ptr]),
-    "tsgu_segment_sum": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_sinkhorn_cpu.py holds it
-# against the header)
-STAGED_SINKHORN = {"tsgu_hip_sinkhorn.h": SIGNATURES_SINKHORN}
-
-# the additive entries of csrc/tsgu_hip_semiring.h (same library, same ABI version): the eleventh STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI` and the ten registries above)
-SIGNATURES_SEMIRING = {
-    "tsgu_semiring_geometry": (_int, [_int, _i64, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "tsgu_csr_semiring_mm": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr,
-                                    _i64, _int, _ptr]),
-    "tsgu_csr_semiring_mm_bwd_values": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64,
-                                               _ptr, _i64, _i64, _ptr, _int, _ptr]),
-    "tsgu_csr_semiring_mm_bwd_dense": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr,
-                                              _i64, _ptr, _i64, _i64, _ptr, _i64, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_semiring_cpu.py holds it
-# against the header)
-STAGED_SEMIRING = {"tsgu_hip_semiring.h": SIGNATURES_SEMIRING}
-
-# the additive entries of csrc/tsgu_hip_gat.h (same library, same ABI version): the twelfth STAGED header, in a registry of its own
-# for the same reason (tests pin `ABI` and the eleven registries above)
-SIGNATURES_GAT = {
-    "tsgu_gat_geometry": (_int, [_int, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "tsgu_csr_gat_forward": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr,
-                                    _int, _int, _dbl, _ptr, _i64, _ptr, _int, _ptr]),
-    "tsgu_csr_gat_backward_rows": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
-                                          _ptr, _ptr, _i64, _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _int, _ptr]),
-    "tsgu_csr_gat_backward_cols": (_int, [_int, _int, _int, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
-                                          _ptr, _ptr, _i64, _ptr, _ptr, _int, _int, _dbl, _ptr, _i64, _ptr, _int, _ptr]),
-    "tsgu_gat_fold": (_int, [_int, _ptr, _i64, _int, _int, _ptr, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_gat_cpu.py holds it against
-# the header)
-STAGED_GAT = {"tsgu_hip_gat.h": SIGNATURES_GAT}
-
-# the additive entries of csrc/tsgu_hip_conv.h (same library, same ABI version): the thirteenth STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI` and the twelve registries above)
-SIGNATURES_CONV = {
-    "tsgu_neighbor_mm_geometry": (_int, [_int, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
-                                         ctypes.POINTER(_i64)]),
-    "tsgu_neighbor_mm": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64,
-                                _int, _ptr]),
-    "tsgu_neighbor_mm_grad_w": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _int,
-                                       _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_conv_cpu.py holds it against
-# the header)
-STAGED_CONV = {"tsgu_hip_conv.h": SIGNATURES_CONV}
-
-# the additive entries of csrc/tsgu_hip_selinv.h (same library, same ABI version): the fourteenth STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI` and the thirteen registries above)
-SIGNATURES_SELINV = {
-    "tsgu_csc_selinv_work_bytes": (_i64, [_int, _i64, _i64]),
-    "tsgu_csc_selinv_geometry": (_int, [_int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "tsgu_csc_selinv": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_selinv_cpu.py holds it
-# against the header)
-STAGED_SELINV = {"tsgu_hip_selinv.h": SIGNATURES_SELINV}
-
-# the additive entries of csrc/tsgu_hip_lsmr.h (same library, same ABI version): the fifteenth STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI` and the fourteen registries above)
-SIGNATURES_LSMR = {
-    "tsgu_lsmr_scal_rows": (_int, []),
-    "tsgu_lsmr_scalar": (_int, [_int, _int, _ptr, _i64, _ptr, _ptr, _ptr, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _int, _ptr]),
-    "tsgu_lsmr_vector": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_lsmr_cpu.py holds it against the
-# header)
-STAGED_LSMR = {"tsgu_hip_lsmr.h": SIGNATURES_LSMR}
-
-# the additive entries of csrc/tsgu_hip_band.h (same library, same ABI version): the sixteenth STAGED header, in a registry of its
-# own for the same reason (tests pin `ABI` and the fifteen registries above)
-SIGNATURES_BAND = {
-    "tsgu_csr_band_geometry": (_int, [_int, _i64, _i64, _int, _int, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
-    "tsgu_csr_band_sptrsm_work_bytes": (_i64, [_int, _i64, _i64, _int, _int, _int]),
-    "tsgu_csr_band_sptrsm": (_int, [_int, _int, _i64, _i64, _ptr, _ptr, _ptr, _int, _int, _int, _int, _ptr, _i64, _ptr, _i64, _i64, _ptr, _int,
-                                    _int, _int, _ptr]),
-}
-
-# header of csrc/ -> its table: bound by `load_library` after the registries above (tests/test_sparse_banded_cpu.py holds it
-# against the header)
-STAGED_BAND = {"tsgu_hip_band.h": SIGNATURES_BAND}
-
-# rows of the LSMR scalar block (csrc/tsgu_hip_lsmr.h) that utils/lsmr.py fills before the first step
+# rows of the LSMR scalar block (include/tsgu_hip_lsmr.h) that utils/lsmr.py fills before the first step
 LSMR_ROW = {"alpha": 0, "beta": 1, "alphabar": 2, "rho": 3, "rhobar": 4, "cbar": 5, "zetabar": 8, "betadd": 9, "rhodold": 11,
             "norm_a2": 15, "minrbar": 17, "normb": 18, "s_prod": 22, "s_self": 23}
 
@@ -507,11 +445,7 @@ def load_library():
         # torch has already loaded its libamdhip64.so (same SONAME), so the kernels register
         # with the runtime that owns torch's streams and allocations.
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for table in (*ABI.values(), *STAGED.values(), *STAGED_AMG.values(), *STAGED_GMRES.values(),
-                      *STAGED_COLOR.values(), *STAGED_QUADRATURE.values(), *STAGED_CIQ.values(), *STAGED_EXPM.values(),
-                      *STAGED_TOPK.values(), *STAGED_SEMI.values(), *STAGED_SINKHORN.values(),
-                      *STAGED_SEMIRING.values(), *STAGED_GAT.values(), *STAGED_CONV.values(), *STAGED_SELINV.values(),
-                      *STAGED_LSMR.values(), *STAGED_BAND.values()):
+        for table in ABI.values():
             for name, (res, args) in table.items():
                 fn = getattr(lib, name)  # AttributeError => header/library mismatch, fail loudly
                 fn.restype = res
@@ -1137,7 +1071,7 @@ def sinkhorn_workspace_bytes(dtype: torch.dtype, nnz: int) -> int:
 
 
 def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
-    return torch.float32 if dtype == torch.bfloat16 else dtype
+    return torch.float64 if dtype == torch.float64 else torch.float32
 
 
 def _sinkhorn_operands(what: str, dev, val, index, vectors, workspace):
@@ -1252,10 +1186,6 @@ def _attention_walk(walk, bias, *dense):
     return dev
 
 
-def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
-    return torch.float64 if dtype == torch.float64 else torch.float32
-
-
 def csr_attention(walk, bias, Q, K, V, heads: int, d: int, scale: float):
     """(O [n, heads·d], lse [n, heads] in the accumulator type) of attention over the pattern walked by rows as
     ``walk = (ptr, idx, perm or None)``; bias: the pattern's value array (at perm[k] for entry k) or None."""
@@ -1352,10 +1282,6 @@ def semiring_geometry(dtype: torch.dtype, p: int):
     """(rows per workgroup, entries of one staging pass, columns per grid.z slice) of the semiring product kernels for `p` columns
     of value type `dtype` with 16-byte aligned operands: the sizes at which their walk changes path.  Host only."""
     return _query("tsgu_semiring_geometry", _VTYPE[dtype], int(p))
-
-
-def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
-    return torch.float64 if dtype == torch.float64 else torch.float32
 
 
 def _semiring_operands(index_arrays, val, dense, C_acc=None, arg=None):
@@ -1877,7 +1803,7 @@ BAND_MAX_WIDTH = 8
 
 def band_geometry(dtype: torch.dtype, n: int, p: int, w: int, chunk_rows=None, group_chunks=None):
     """(rows of a chunk, chunk summaries of a carry group, longest chain one workgroup walks) of the banded solve: pure functions of
-    (n, p, w, dtype) and the two overrides (csrc/tsgu_hip_band.h)."""
+    (n, p, w, dtype) and the two overrides (include/tsgu_hip_band.h)."""
     return _query("tsgu_csr_band_geometry", _VTYPE[dtype], int(n), int(p), int(w), int(chunk_rows or 0), int(group_chunks or 0))
 
 
@@ -1957,7 +1883,7 @@ def selinv_geometry(dtype: torch.dtype):
 
 def csc_selinv(colptr, rowidx, perm, diag_pos, val, n: int, D=None, wg_per_cu: int = 1):
     """The entries of (L·Lᵀ)⁻¹ (``D`` None; `diag_pos` the CSC position of every column's diagonal) or ((L+I)·D·(L+I)ᵀ)⁻¹ (L strictly
-    lower, `diag_pos` None) at the stored positions of L, given by its columns (csrc/tsgu_hip_selinv.h): `perm` the position of
+    lower, `diag_pos` None) at the stored positions of L, given by its columns (include/tsgu_hip_selinv.h): `perm` the position of
     every CSC entry in `val`.  Ascending unique rows, nothing above the diagonal — the caller's plan has checked that.  Returns
     (out, diag, info): `out` in the order of `val`, `diag` the diagonal of the inverse (None without ``D``), `info` two device int64
     (1 + the lowest column with a zero / non-finite pivot, 1 + the lowest column with a lookup that missed).  Nothing is read back here
@@ -2022,7 +1948,7 @@ def csr_fsai(a_ptr, a_idx, a_val, s_ptr, s_idx, n: int, order=None, wg_per_cu: i
 
 
 def tall_geometry(dtype: torch.dtype, n: int = 0, a: int = 0, b: int = 0):
-    """(kmax, wmax, rows_per_workgroup, workspace_bytes) of the tall-skinny kernels (csrc/tsgu_hip_lobpcg.h): the widest block, the
+    """(kmax, wmax, rows_per_workgroup, workspace_bytes) of the tall-skinny kernels (include/tsgu_hip_lobpcg.h): the widest block, the
     widest operand of the Gram kernel, the rows of a chunk, and the bytes `tall_gram` needs for `n` rows and an `a` x `b` result
     (`lobpcg_residual`: a = k, b = 1)."""
     return _query("tsgu_tall_geometry", _VTYPE[dtype], int(n), int(a), int(b))
@@ -2113,7 +2039,7 @@ def lobpcg_residual(AX, X, lam, out=None, workspace=None, workgroups: int = 0):
 
 def amg_geometry():
     """(group widths the hop accepts — the powers of two between the library's limits —, column tile of the affine product)
-    (csrc/tsgu_hip_amg.h).  Host only."""
+    (include/tsgu_hip_amg.h).  Host only."""
     lo, hi, tile = _query("tsgu_amg_geometry")
     widths = []
     while lo <= hi:
@@ -2148,7 +2074,7 @@ AMG_INIT, AMG_ROUND, AMG_ROOTS = 0, 1, 2
 
 
 def amg_mis2_update(mode: int, n: int, key=None, t=None, out=None, undecided=None, device=None):
-    """One node-wise step of the MIS-2 aggregation (csrc/tsgu_hip_amg.h): AMG_INIT writes the initial keys, AMG_ROUND applies the
+    """One node-wise step of the MIS-2 aggregation (include/tsgu_hip_amg.h): AMG_INIT writes the initial keys, AMG_ROUND applies the
     state machine to (key, t = hop(hop(key))) and sets the device word `undecided` (zeroed by the caller) when a node stays
     undecided, AMG_ROOTS keeps the roots' keys and zeroes the rest.  Returns `out` (AMG_ROUND may write `key` in place)."""
     dev = require_device(key, t, out, undecided) or device
@@ -2165,7 +2091,7 @@ def amg_mis2_update(mode: int, n: int, key=None, t=None, out=None, undecided=Non
 
 def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, w=None, alpha: float = 1.0, out=None):
     """out = C + alpha·w∘(B − A·X) for the CSR matrix (ptr, idx, val) of shape (n_rows, n_cols) and row-major X (n_cols, p); C, B
-    (n_rows, p) and w (n_rows,) are optional (None: 0, 0 and 1).  One launch (csrc/tsgu_hip_amg.h).  `out` may be C or B; it may
+    (n_rows, p) and w (n_rows,) are optional (None: 0, 0 and 1).  One launch (include/tsgu_hip_amg.h).  `out` may be C or B; it may
     not overlap X (the library refuses it).  float32 and float64."""
     if val.dtype not in FACTOR_DTYPES:
         raise TypeError(f"tsgu_csr_affine_spmm: float32 and float64 values only, got {val.dtype}")
@@ -2192,7 +2118,7 @@ def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, 
 
 def color_geometry():
     """(group widths of the colouring round and check, colours per window, group widths of the sweep, column tile of the sweep)
-    (csrc/tsgu_hip_color.h).  Host only."""
+    (include/tsgu_hip_color.h).  Host only."""
     lo, hi, window, slo, shi, tile = _query("tsgu_color_geometry")
     pows = lambda a, b: tuple(a << k for k in range(8) if (a << k) <= b)      # noqa: E731
     return pows(lo, hi), window, pows(slo, shi), tile
@@ -2217,7 +2143,7 @@ def _color_vector(what: str, n: int, *vectors):
 
 def csr_color_round(ptr, idx, tptr, tidx, colors, n: int, out, undecided, group: int = 8):
     """One round of the greedy multicolouring on the pattern (ptr, idx) and its transpose (tptr, tidx; None when the pattern is
-    structurally symmetric) (csrc/tsgu_hip_color.h): `out` receives the colours after the round, `undecided` (an int64 word the
+    structurally symmetric) (include/tsgu_hip_color.h): `out` receives the colours after the round, `undecided` (an int64 word the
     caller zeroed) becomes non-zero when a node stays uncoloured.  `group`: lanes per node, one of `color_geometry()[0]`."""
     dev = require_device(ptr, idx, tptr, tidx, colors, out, undecided)
     ptr, idx, tptr, tidx, nnz_t = _color_pattern("tsgu_csr_color_round", ptr, idx, tptr, tidx, n)
@@ -2232,7 +2158,7 @@ def csr_color_round(ptr, idx, tptr, tidx, colors, n: int, out, undecided, group:
 
 def csr_color_check(ptr, idx, tptr, tidx, colors, n: int, n_colors: int, group: int = 8):
     """A device int64: 0 when `colors` is a colouring of the pattern with `n_colors` colours, else 1 + the lowest row whose colour
-    is outside [0, n_colors) or held by a neighbour (csrc/tsgu_hip_color.h).  Nothing is read back here."""
+    is outside [0, n_colors) or held by a neighbour (include/tsgu_hip_color.h).  Nothing is read back here."""
     dev = require_device(ptr, idx, tptr, tidx, colors)
     ptr, idx, tptr, tidx, nnz_t = _color_pattern("tsgu_csr_color_check", ptr, idx, tptr, tidx, n)
     _color_vector("tsgu_csr_color_check", n, colors)
@@ -2248,7 +2174,7 @@ SWEEP_DIVIDE, SWEEP_UNIT, SWEEP_SCALED = 0, 1, 2
 
 def csr_color_sweeps(mode: int, begin, end, idx, diag, val, B, X, classes, vmap=None, bmap=None, out=None, out_rows=None, group: int = 8):
     """One triangular sweep by colour classes, in place in the workspace X (n, p): one launch of `tsgu_csr_color_sweep`
-    (csrc/tsgu_hip_color.h) per (row0, row1) of `classes`, in their order.  For the rows of a class,
+    (include/tsgu_hip_color.h) per (row0, row1) of `classes`, in their order.  For the rows of a class,
     x[i] = (B[bmap(i)] − Σ_{e in [begin[i], end[i])} val[vmap(e)]·x[idx[e]]) / val[vmap(diag[i])] (SWEEP_DIVIDE), without the division
     (SWEEP_UNIT, diag None) or with the sum alone divided (SWEEP_SCALED); `out`, when given, also receives x[i] in row out_rows(i).
     The operands are checked once for all classes and nothing is copied: they are contiguous in the way the plan made them."""
@@ -2445,7 +2371,7 @@ def coldot(X, Y):
 
 def gmres_geometry(dtype: torch.dtype, n: int, p: int):
     """(restart cap, basis group size, rows per workgroup, partial rows per launch) of the GMRES kernels for an (n, p) block
-    (csrc/tsgu_hip_gmres.h).  Host only; a width the lane geometry does not cover raises with the rule."""
+    (include/tsgu_hip_gmres.h).  Host only; a width the lane geometry does not cover raises with the rule."""
     fn = load_library().tsgu_gmres_geometry
     cap, group, rows, parts = _int(0), _int(0), _i64(0), _i64(0)
     rc = fn(_VTYPE[dtype], n, p, ctypes.byref(cap), ctypes.byref(group), ctypes.byref(rows), ctypes.byref(parts))
@@ -2457,7 +2383,7 @@ def gmres_geometry(dtype: torch.dtype, n: int, p: int):
 
 
 def gmres_state_rows(m: int) -> dict:
-    """First row of every field of the GMRES `scal` state for restart length m, and the row count (csrc/tsgu_hip_gmres.h)."""
+    """First row of every field of the GMRES `scal` state for restart length m, and the row count (include/tsgu_hip_gmres.h)."""
     return {"threshold": 0, "estimate": 1, "hnorm": 2, "g": 3, "cs": m + 4, "sn": 2 * m + 4, "y": 3 * m + 4, "h": 4 * m + 4,
             "coef": 5 * m + 4, "R": 6 * m + 4, "rows": m * m + 6 * m + 4}
 
@@ -2639,7 +2565,7 @@ def csr_row_sumsq_backward(crow, col, perm, val, w, g, n_rows: int):
     return grad
 
 
-# ---- Lanczos quadrature and Rademacher probes (csrc/tsgu_hip_quadrature.h; sparse_logdet.py) ------------------------------------
+# ---- Lanczos quadrature and Rademacher probes (include/tsgu_hip_quadrature.h; sparse_logdet.py) ------------------------------------
 QUAD_CG, QUAD_ENTRIES = 0, 1                                   # `kind`: rows of CG coefficients | rows of (diagonal, off-diagonal)
 QUAD_LOG, QUAD_RECIPROCAL, QUAD_IDENTITY, QUAD_ONE = 0, 1, 2, 3  # `fn`
 QUAD_NO_WORK_ROWS = 64                                         # the header's promise: r up to here never reads `work`
@@ -2691,7 +2617,7 @@ def rademacher_fill(n: int, p: int, seed: int, dtype: torch.dtype, device) -> to
     return out
 
 
-# ---- contour-quadrature update (csrc/tsgu_hip_ciq.h; sparse_sqrt.py) ---------------------------------------------------------------
+# ---- contour-quadrature update (include/tsgu_hip_ciq.h; sparse_sqrt.py) ---------------------------------------------------------------
 def ciq_geometry(dtype: torch.dtype, n: int, p: int):
     """(shift cap, plane alignment in elements, rows per workgroup, workgroups) of tsgu_ciq_update for an (n, p) block.  Host only;
     a width the lane geometry does not cover raises with the rule."""
@@ -2706,7 +2632,7 @@ def ciq_geometry(dtype: torch.dtype, n: int, p: int):
 
 
 def ciq_update(zc, zp, wpp, wp, shift_stride: int, acc, keep, scal, omega, done, flags) -> None:
-    """One tsgu_ciq_update launch on the (n, p) state `zc`: see csrc/tsgu_hip_ciq.h.  `keep` may be None."""
+    """One tsgu_ciq_update launch on the (n, p) state `zc`: see include/tsgu_hip_ciq.h.  `keep` may be None."""
     dev = require_device(zc, zp, wpp, wp, acc, keep, scal, omega, done, flags)
     n, p = zc.shape
     launch("tsgu_ciq_update", dev, vtype_of(zc), n, p, omega.numel(), zc, zp, wpp, wp, int(shift_stride), acc, keep, scal, omega, done,
@@ -2714,12 +2640,12 @@ def ciq_update(zc, zp, wpp, wp, shift_stride: int, acc, keep, scal, omega, done,
 
 
 def ciq_stop(scal, tol: float, est, done, flags) -> None:
-    """One tsgu_ciq_stop launch on scal [S][12][p]: see csrc/tsgu_hip_ciq.h."""
+    """One tsgu_ciq_stop launch on scal [S][12][p]: see include/tsgu_hip_ciq.h."""
     dev = require_device(scal, est, done, flags)
     launch("tsgu_ciq_stop", dev, vtype_of(scal), scal.size(2), scal.size(0), scal, float(tol), est, done, flags)
 
 
-# ---- Chebyshev recurrence (csrc/tsgu_hip_expm.h; sparse_expm.py) --------------------------------------------------------------------
+# ---- Chebyshev recurrence (include/tsgu_hip_expm.h; sparse_expm.py) --------------------------------------------------------------------
 def expm_geometry(dtype: torch.dtype, n: int, p: int):
     """(time cap, chunk cap, plane alignment in elements, rows per workgroup, workgroups) of tsgu_cheb_step / tsgu_cheb_combine for an
     (n, p) block.  Host only; a width the lane geometry does not cover raises with the rule."""
@@ -2734,7 +2660,7 @@ def expm_geometry(dtype: torch.dtype, n: int, p: int):
 
 
 def cheb_step(prod, x, prev, alpha: float, beta: float, gamma: float, flags, src=None, src_slot: int = 0, chunk=None, slot: int = 0) -> None:
-    """One tsgu_cheb_step launch on the (n, p) state `prev`: see csrc/tsgu_hip_expm.h.  `prod`, `src` and `chunk` may be None; `src`
+    """One tsgu_cheb_step launch on the (n, p) state `prev`: see include/tsgu_hip_expm.h.  `prod`, `src` and `chunk` may be None; `src`
     and `chunk` are (n, slots, p)."""
     dev = require_device(prod, x, prev, src, chunk, flags)
     n, p = prev.shape
@@ -2744,14 +2670,14 @@ def cheb_step(prod, x, prev, alpha: float, beta: float, gamma: float, flags, src
 
 def cheb_combine(mode: int, chunk, coef, planes, plane_stride: int, flags, accumulate: bool = False) -> None:
     """One tsgu_cheb_combine launch: `chunk` (n, m, p), `coef` (m, T, p), `planes` the T arrays (n, p) `plane_stride` elements apart
-    (mode 0 writes them, mode 1 reads them): see csrc/tsgu_hip_expm.h."""
+    (mode 0 writes them, mode 1 reads them): see include/tsgu_hip_expm.h."""
     dev = require_device(chunk, coef, planes, flags)
     n, m, p = chunk.shape
     launch("tsgu_cheb_combine", dev, vtype_of(chunk), int(mode), int(bool(accumulate)), n, p, m, coef.size(1), chunk, coef, planes,
            int(plane_stride), flags)
 
 
-# ---- top-k of a dense product as CSR arrays (csrc/tsgu_hip_topk.h; sparse_topk.py) --------------------------------------------------
+# ---- top-k of a dense product as CSR arrays (include/tsgu_hip_topk.h; sparse_topk.py) --------------------------------------------------
 TOPK_CAUSAL, TOPK_EXCLUDE_SELF = 1, 2
 
 
@@ -2763,7 +2689,7 @@ def topk_geometry(dtype: torch.dtype, d: int = 1, k: int = 1):
 
 def topk_mm(Q, K, key_bias, k: int, scale: float, flags: int, causal_offset: int, crow, col, val) -> None:
     """One tsgu_topk_mm launch: Q (b, n, d), K (b, m, d) and key_bias (b, m) or None, contiguous; crow (n + 1,) shared by the batch
-    items; col and val (b, nnz) are written.  See csrc/tsgu_hip_topk.h."""
+    items; col and val (b, nnz) are written.  See include/tsgu_hip_topk.h."""
     dev = require_device(Q, K, key_bias, crow, col, val)
     b, n, d = Q.shape
     m = K.size(1)
@@ -2771,7 +2697,7 @@ def topk_mm(Q, K, key_bias, k: int, scale: float, flags: int, causal_offset: int
            itype_of(crow), b, n * d, m * d, m, col.size(1))
 
 
-# ---- 2:4 semi-structured operands (csrc/tsgu_hip_semi.h; sparse_semi_structured.py) --------------------------------------------------
+# ---- 2:4 semi-structured operands (include/tsgu_hip_semi.h; sparse_semi_structured.py) --------------------------------------------------
 # Every wrapper takes 2-D tensors with unit stride in the last dimension (`rowmajor`) and passes the row strides on: sliced views
 # are consumed in place.  `meta` is the int32 (m, 4·ceil(k / 128)) position tensor of the header.
 SEMI_DENSE_T, SEMI_OUT_T = 1, 2

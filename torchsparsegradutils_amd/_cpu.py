@@ -691,7 +691,7 @@ def csr_factor(kind: str, crow: torch.Tensor, col: torch.Tensor, diag_pos: torch
 
 
 def selected_inverse(colptr: torch.Tensor, rowidx: torch.Tensor, perm: torch.Tensor, diag_pos, val: torch.Tensor, n: int, D=None):
-    """The Takahashi recurrence of csrc/tsgu_hip_selinv.h on the CSC view (colptr, rowidx, perm) of a lower factor, column by column
+    """The Takahashi recurrence of include/tsgu_hip_selinv.h on the CSC view (colptr, rowidx, perm) of a lower factor, column by column
     from the right in the value type: targets in descending order, a lookup that misses contributes a zero, a zero or non-finite
     pivot is carried through with IEEE arithmetic.  Reference speed only — one numpy step per stored sub-diagonal entry.  Returns
     (out, diag, info) like `_backend.csc_selinv`."""
@@ -780,7 +780,7 @@ def csr_fsai(a_crow: torch.Tensor, a_col: torch.Tensor, a_val: torch.Tensor, s_c
     return torch.from_numpy(out), torch.tensor(bad, dtype=torch.int64)
 
 
-# ---- the three primitives of the LOBPCG loop (utils/lobpcg.py): csrc/tsgu_hip_lobpcg.h in torch ops -------------------------------
+# ---- the three primitives of the LOBPCG loop (utils/lobpcg.py): include/tsgu_hip_lobpcg.h in torch ops -------------------------------
 
 def tall_gram(Y: torch.Tensor, Z: torch.Tensor, out=None, workspace=None, workgroups: int = 0) -> torch.Tensor:
     """YᵀZ for (n, a) and (n, b) views."""
@@ -829,7 +829,7 @@ def lobpcg_residual(AX: torch.Tensor, X: torch.Tensor, lam: torch.Tensor, out=No
     return R, (R * R).sum(dim=0)
 
 
-# ---- the primitives of the aggregation multigrid (sparse_amg.py): csrc/tsgu_hip_amg.h in torch ops --------------------------------
+# ---- the primitives of the aggregation multigrid (sparse_amg.py): include/tsgu_hip_amg.h in torch ops --------------------------------
 
 _SIGN = -(1 << 63)       # x ^ _SIGN maps the unsigned order of 64-bit words onto the signed order of int64
 
@@ -892,7 +892,7 @@ def csr_affine_spmm(ptr, idx, val, X, n_rows: int, n_cols: int, C=None, B=None, 
     return r if out is None else out.copy_(r)
 
 
-# ---- the primitives of the multicolour ordering (sparse_coloring.py): csrc/tsgu_hip_color.h in torch ops --------------------------
+# ---- the primitives of the multicolour ordering (sparse_coloring.py): include/tsgu_hip_color.h in torch ops --------------------------
 
 def _color_edges(ptr, idx, tptr, tidx, n: int):
     """(u, v) int64: every stored entry (u, v) of A and, when given, of Aᵀ, without the diagonal and the columns outside the matrix."""
@@ -906,7 +906,7 @@ def _color_edges(ptr, idx, tptr, tidx, n: int):
 
 
 def color_greedy(ptr, idx, tptr, tidx, n: int) -> torch.Tensor:
-    """The colouring of csrc/tsgu_hip_color.h by its own rounds: an uncoloured node with no uncoloured neighbour of greater key
+    """The colouring of include/tsgu_hip_color.h by its own rounds: an uncoloured node with no uncoloured neighbour of greater key
     (lowbias32(i), i) takes the smallest colour no neighbour holds.  int32 colours; reference speed only."""
     _cpu_only(ptr, idx, tptr, tidx)
     u, v = _color_edges(ptr, idx, tptr, tidx, n)
@@ -981,7 +981,7 @@ def csr_color_sweeps(mode: int, begin, end, idx, diag, val, B, X, classes, vmap=
     return X
 
 
-# ---- Lanczos quadrature (sparse_logdet.py): csrc/tsgu_hip_quadrature.h in torch ops ------------------------------------------------
+# ---- Lanczos quadrature (sparse_logdet.py): include/tsgu_hip_quadrature.h in torch ops ------------------------------------------------
 
 def rademacher_fill(n: int, p: int, seed: int, dtype: torch.dtype) -> torch.Tensor:
     """The (n, p) block of ±1 of tsgu_rademacher_fill, bit for bit: the sign bit of lowbias32(c + lowbias32(i + s)) with

@@ -1339,7 +1339,7 @@ _COLOR_POLL_ROUNDS = 4       # colouring rounds between two reads of the "still 
 
 
 class SweepTable:
-    """One triangle of a pattern as the colour sweep takes it (csrc/tsgu_hip_color.h): per-row `begin` / `end` positions into `idx`
+    """One triangle of a pattern as the colour sweep takes it (include/tsgu_hip_color.h): per-row `begin` / `end` positions into `idx`
     and the diagonal's position `diag`, all contiguous and of one index dtype."""
 
     __slots__ = ("begin", "end", "idx", "diag")
@@ -1437,7 +1437,7 @@ def _color_lists(g: RowGather):
 
 
 def greedy_colors(g: RowGather, group: Optional[int] = None) -> torch.Tensor:
-    """The colours of the pattern (int32) by the rounds of csrc/tsgu_hip_color.h; `group`: lanes per node (the result is the same)."""
+    """The colours of the pattern (int32) by the rounds of include/tsgu_hip_color.h; `group`: lanes per node (the result is the same)."""
     from . import _backend as _be
 
     n, dev = g.n_rows, g.col.device
@@ -1480,7 +1480,7 @@ def check_colors(g: RowGather, colors: torch.Tensor, n_colors: int) -> int:
 
 
 def coloring_plan(g: RowGather, colors=None) -> ColoringPlan:
-    """The ColoringPlan of a 2-D square pattern: the greedy colouring of csrc/tsgu_hip_color.h (cached with the pattern), or the
+    """The ColoringPlan of a 2-D square pattern: the greedy colouring of include/tsgu_hip_color.h (cached with the pattern), or the
     caller's `colors` (validated: ValueError naming the lowest conflicting row; not cached).  Torch ops and a handful of host reads
     at plan time; none of it is hot."""
     if g.batch is not None or g.n_rows != g.n_cols:

@@ -1,7 +1,7 @@
 // Entry points of the aggregation multigrid kernels (tsgu_hip_amg.h; kernels: amg_impl.h).
 #include "amg_impl.h"
 
-#include "tsgu_hip_amg.h"
+#include "../../include/tsgu_hip_amg.h"
 
 namespace tsgu {
 

@@ -1,7 +1,7 @@
-// Entry points of the banded triangular solve (csrc/tsgu_hip_band.h; kernels and geometry: band_impl.h).
+// Entry points of the banded triangular solve (include/tsgu_hip_band.h; kernels and geometry: band_impl.h).
 #include "band_impl.h"
 
-#include "tsgu_hip_band.h"
+#include "../../include/tsgu_hip_band.h"
 
 namespace tsgu {
 

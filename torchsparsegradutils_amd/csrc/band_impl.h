@@ -1,4 +1,4 @@
-// Banded triangular solves in logarithmic depth (csrc/tsgu_hip_band.h; entries: band.hip; caller: sparse_banded_solve.py).
+// Banded triangular solves in logarithmic depth (include/tsgu_hip_band.h; entries: band.hip; caller: sparse_banded_solve.py).
 //
 // T = op(A) is triangular with |row − col| <= W on the solved side, so T x = b is a linear recurrence of order W.  The rows are
 // walked in TRAVERSAL order (step g = row for an ascending solve, n − 1 − row for a descending one) and cut into chunks of R

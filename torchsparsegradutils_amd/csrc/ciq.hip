@@ -1,6 +1,6 @@
 // K11: entry points of the contour-quadrature update (ciq_impl.h; contracts in tsgu_hip_ciq.h).
 #include "ciq_impl.h"
-#include "tsgu_hip_ciq.h"
+#include "../../include/tsgu_hip_ciq.h"
 
 using namespace tsgu;
 

@@ -1,7 +1,7 @@
 // Entry points of the multicolour ordering kernels (tsgu_hip_color.h; kernels: color_impl.h).
 #include "color_impl.h"
 
-#include "tsgu_hip_color.h"
+#include "../../include/tsgu_hip_color.h"
 
 namespace tsgu {
 

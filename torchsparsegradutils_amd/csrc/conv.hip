@@ -1,6 +1,6 @@
-// neighbor_mm: the extern "C" entry points of csrc/tsgu_hip_conv.h (kernels: conv_impl.h).
+// neighbor_mm: the extern "C" entry points of include/tsgu_hip_conv.h (kernels: conv_impl.h).
 #include "conv_impl.h"
-#include "tsgu_hip_conv.h"
+#include "../../include/tsgu_hip_conv.h"
 
 using namespace tsgu;
 

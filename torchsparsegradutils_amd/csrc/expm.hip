@@ -1,6 +1,6 @@
 // K12: entry points of the Chebyshev recurrence of sparse_expm_mm (expm_impl.h; contracts in tsgu_hip_expm.h).
 #include "expm_impl.h"
-#include "tsgu_hip_expm.h"
+#include "../../include/tsgu_hip_expm.h"
 
 using namespace tsgu;
 

@@ -2,7 +2,7 @@
 // and column pass of both kinds, the datt fold) and the extern "C" entry points of tsgu_hip_gat.h.
 #include "gat_impl.h"
 
-#include "tsgu_hip_gat.h"
+#include "../../include/tsgu_hip_gat.h"
 
 using namespace tsgu;
 

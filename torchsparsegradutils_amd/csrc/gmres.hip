@@ -1,6 +1,6 @@
 // K8: entry points of the GMRES Arnoldi kernels (gmres_impl.h; contracts in tsgu_hip_gmres.h).
 #include "gmres_impl.h"
-#include "tsgu_hip_gmres.h"
+#include "../../include/tsgu_hip_gmres.h"
 
 using namespace tsgu;
 

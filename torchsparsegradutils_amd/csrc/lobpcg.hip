@@ -1,7 +1,7 @@
 // Entry points of the tall-skinny dense kernels of the LOBPCG loop (tsgu_hip_lobpcg.h; kernels: lobpcg_impl.h).
 #include "lobpcg_impl.h"
 
-#include "tsgu_hip_lobpcg.h"
+#include "../../include/tsgu_hip_lobpcg.h"
 
 namespace tsgu {
 

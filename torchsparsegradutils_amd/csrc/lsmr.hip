@@ -18,6 +18,7 @@
 // flags, int32 [2 + 2 p]: [0] stop: every column is done | [1] iterations run | [2, 2 + p) done | [2 + p, 2 + 2 p) iterations of
 //   the column (the last iteration that began while it was live)
 #include "krylov_common.h"
+#include "../../include/tsgu_hip_lsmr.h"
 
 namespace tsgu {
 

@@ -1,6 +1,6 @@
 // K10: entry points of the Lanczos quadrature and the Rademacher fill (quadrature_impl.h; contracts in tsgu_hip_quadrature.h).
 #include "quadrature_impl.h"
-#include "tsgu_hip_quadrature.h"
+#include "../../include/tsgu_hip_quadrature.h"
 
 using namespace tsgu;
 

@@ -1,7 +1,7 @@
-// Entry points of the selected inversion (csrc/tsgu_hip_selinv.h; kernels: selinv_impl.h).
+// Entry points of the selected inversion (include/tsgu_hip_selinv.h; kernels: selinv_impl.h).
 #include "selinv_impl.h"
 
-#include "tsgu_hip_selinv.h"
+#include "../../include/tsgu_hip_selinv.h"
 
 namespace tsgu {
 

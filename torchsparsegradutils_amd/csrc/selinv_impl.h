@@ -1,4 +1,4 @@
-// Takahashi selected inversion as ONE persistent, dependency-driven launch (csrc/tsgu_hip_selinv.h).
+// Takahashi selected inversion as ONE persistent, dependency-driven launch (include/tsgu_hip_selinv.h).
 //
 // Given the lower factor L of Q = L·Lᵀ (or the unit factor and D of Q = (L+I)·D·(L+I)ᵀ) by its COLUMNS (CSC: ascending rows, the
 // diagonal first), the entries of Σ = Q⁻¹ on the pattern of L follow column by column from the right.  With s(i) = s_0 < s_1 < … the

@@ -1,6 +1,6 @@
 // K14: entry points of the 2:4 semi-structured operand (semi_impl.h; contracts in tsgu_hip_semi.h).
 #include "semi_impl.h"
-#include "tsgu_hip_semi.h"
+#include "../../include/tsgu_hip_semi.h"
 
 using namespace tsgu;
 

@@ -2,7 +2,7 @@
 // semirings × forward, values pass, dense pass) and the extern "C" entry points of tsgu_hip_semiring.h.
 #include "semiring_impl.h"
 
-#include "tsgu_hip_semiring.h"
+#include "../../include/tsgu_hip_semiring.h"
 
 using namespace tsgu;
 

@@ -2,7 +2,7 @@
 // and the extern "C" entry points of tsgu_hip_sinkhorn.h.
 #include "sinkhorn_impl.h"
 
-#include "tsgu_hip_sinkhorn.h"
+#include "../../include/tsgu_hip_sinkhorn.h"
 
 using namespace tsgu;
 

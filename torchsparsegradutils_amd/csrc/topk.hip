@@ -2,7 +2,7 @@
 #include <cmath>
 
 #include "topk_impl.h"
-#include "tsgu_hip_topk.h"
+#include "../../include/tsgu_hip_topk.h"
 
 using namespace tsgu;
 

@@ -9,7 +9,7 @@ convergent iteration, so ``M`` is symmetric positive definite and is what ``line
 reference package has no counterpart.
 
 Two primitives carry everything that is not a torch op or a ``sparse_spgemm`` (``csrc/amg_impl.h``, C ABI in
-``csrc/tsgu_hip_amg.h``; for CPU operands the torch-op forms of ``_cpu.py``, the same Python code above them):
+``include/tsgu_hip_amg.h``; for CPU operands the torch-op forms of ``_cpu.py``, the same Python code above them):
 
 ``hop``      ``out[i] = max(in[i], max_{j in row i} in[j])`` over unsigned 64-bit keys on a CSR pattern: the MIS-2 rounds and the
              assignment of the nodes to their roots.  A max is exact, so the aggregates are a pure function of the pattern: the

@@ -10,7 +10,7 @@ than the natural ones (DESIGN.md §4 has the measurements).
 
 The colouring is a pure function of the pattern.  The neighbours of ``i`` are the ``j ≠ i`` with ``(i, j)`` or ``(j, i)`` stored;
 node ``i`` has the key ``(lowbias32(i), i)``; the nodes are visited in descending key and each takes the smallest colour no
-coloured neighbour holds.  The kernels reach that result by rounds (``csrc/color_impl.h``, C ABI in ``csrc/tsgu_hip_color.h``); for
+coloured neighbour holds.  The kernels reach that result by rounds (``csrc/color_impl.h``, C ABI in ``include/tsgu_hip_color.h``); for
 CPU operands the torch-op forms of ``_cpu.py`` run under the same Python code.  Everything else about the ordering is a plan
 cached with the pattern (``_pattern.coloring_plan``).
 

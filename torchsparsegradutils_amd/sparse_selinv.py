@@ -3,7 +3,7 @@
 The Takahashi recurrence (Takahashi, Fagan & Chin 1973; Erisman & Tinney 1975): what INLA-style inference builds the posterior
 marginal variances of a Gaussian Markov random field on, and the exact gradient of ``log det Q`` on ``Q``'s pattern.  It costs what
 the factorisation cost and never forms an ``n × n`` matrix; the reference package has no counterpart.  The recurrence is ONE persistent,
-dependency-driven launch on the gfx950 (``csrc/selinv_impl.h``, C ABI in ``csrc/tsgu_hip_selinv.h``); everything about the pattern
+dependency-driven launch on the gfx950 (``csrc/selinv_impl.h``, C ABI in ``include/tsgu_hip_selinv.h``); everything about the pattern
 (the check, the column view of ``L``) is a plan cached with it (``_pattern.selinv_plan``).
 
 The pattern of ``L`` must be closed under elimination: for every column, every pair of rows stored below the diagonal is itself a

@@ -8,7 +8,7 @@ A 2:4 matrix keeps two of every four consecutive entries of a row.  ``SemiStruct
 (``0 <= p0 < p1 <= 3``, the kept positions) per group of four.  Group ``g`` of a row (dense columns ``4g .. 4g+3``) lives, with
 ``stage = g // 32``, ``s = (g % 32) // 8``, ``q = (g % 8) // 2``, ``h = g % 2``, in bits ``[8s + 4h, 8s + 4h + 4)`` of word ``4·stage + q``:
 word ``q`` of a stage is the position register of lane quarter ``q`` of ``v_smfmac_f32_16x16x32_bf16`` and byte ``s`` what the ``s``-th
-instruction of a 128-column stage selects (``csrc/tsgu_hip_semi.h``).  Groups past ``k`` hold ``0x4``.  Read the pattern through
+instruction of a 128-column stage selects (``include/tsgu_hip_semi.h``).  Groups past ``k`` hold ``0x4``.  Read the pattern through
 :meth:`SemiStructured.indices`, not through the packed words.
 
 GPU operands run the kernels of ``csrc/semi_impl.h``: products on a dense LDS image of ``A`` with zeros at the dropped positions

@@ -151,7 +151,7 @@ def _not_spd(who: str):
 
 def _estimate_bounds(who: str, A: torch.Tensor, lanczos_steps: int, seed: int):
     """(0.5·θ_min, 1.1·θ_max) of the Lanczos matrix of (A, one Rademacher column) after ``lanczos_steps`` CG steps: T from the CG
-    coefficients by the "kind 0" formulas of csrc/tsgu_hip_quadrature.h, its eigenvalues on the host."""
+    coefficients by the "kind 0" formulas of include/tsgu_hip_quadrature.h, its eigenvalues on the host."""
     n = A.size(0)
     steps = max(1, min(int(lanczos_steps), n))
     z = _be.rademacher_fill(n, 1, seed, A.dtype, A.device)

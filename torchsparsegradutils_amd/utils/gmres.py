@@ -1,7 +1,7 @@
 """``gmres`` — restarted GMRES(m), right-preconditioned, for general (non-symmetric) ``A``.  The reference has no counterpart:
 the interface follows ``bicgstab`` (a settings tuple, ``max(abstol, reltol·‖r₀‖)`` as the threshold of every column).
 
-All right-hand sides advance in lock-step on the Arnoldi kernels of ``csrc/gmres.hip`` (contracts: ``csrc/tsgu_hip_gmres.h``):
+All right-hand sides advance in lock-step on the Arnoldi kernels of ``csrc/gmres.hip`` (contracts: ``include/tsgu_hip_gmres.h``):
 every column has its own basis, Hessenberg column, rotations, stopping point and iteration count on the device, and a finished
 column is frozen.  An inner step orthogonalises with classical Gram–Schmidt and one re-orthogonalisation (two global reductions
 instead of the ``j + 1`` dependent ones of modified Gram–Schmidt).  One restart cycle is one chunk of ``_graph.run_chunked``: the

@@ -267,7 +267,7 @@ def lsmr(
 def _lsmr_fused(mat, rmat, B: torch.Tensor, x0, n: int, damp: float, atol: float, btol: float, ctol: float, eps: float,
                 maxiter: int, own: bool):
     """LSMR on the K8 kernels (csrc/lsmr.hip) for the (m, p) right-hand sides `B`: returns (x, per-column iteration counts,
-    every column met a stopping test).  u~ = β u and v~ = α v are kept unnormalised; scalars and flags as csrc/tsgu_hip_lsmr.h
+    every column met a stopping test).  u~ = β u and v~ = α v are kept unnormalised; scalars and flags as include/tsgu_hip_lsmr.h
     lays them out."""
     lib = _be.load_library()
     m, p = B.shape
